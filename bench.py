@@ -1,23 +1,28 @@
 #!/usr/bin/env python3
 """bench.py -- CHAP training throughput on MI355X (BASELINE.json metric: training volumes/sec).
 
-    python bench.py --gpus N --steps K --warmup W [--config 2d|3d] [--dtype bf16|fp32]
+    python bench.py --gpus N --steps K --warmup W [--config 2d|3d] [--dtype bf16|fp32] [--dump-outputs DIR] [--full]
 
 One "step" = one full iteration of train() (code/train_ours_2D.py:301-389): pass A on the unlabeled
 half, BCP mix, pass B fwd/bwd with the four mix_loss terms, VAT (K power iterations + final pass),
 SGD -- on a synthetic fixed-seed batch already resident in HBM.  N=1 workload = BASELINE config 1
 (ACDC 2D DualDecoder, bs=24 = 12 lab + 12 unlab, 256x256, 1 perturbation step, bf16).
-Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` and `cpu_baseline`.
+Rank 0 prints ONE JSON line (contract in the task statement).  A plain run sets up, warms up, times the
+K steps and prints the line; `--full` adds `roofline`, `cpu_baseline` and (default configuration)
+`extra_configs`, each measured in runs of its own after the timed steps.  `--dump-outputs DIR` writes
+what the last timed step computed (losses, model state) as DIR/<name>.npy.
 """
 import argparse
 import json
 import os
+import random
 import sys
 import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 T_START = time.perf_counter()
@@ -46,9 +51,13 @@ def parse():
                     "folding the buckets and all-reducing once at the end (default: measured faster, see DESIGN.md section 6)")
     ap.add_argument("--master-port", type=int, default=29531)
     ap.add_argument("--set", action="append", default=[], metavar="KEY=VALUE", help="override a ChapStep argument (experiments), e.g. --set vat_early=0")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also measure the roofline probes, the CPU baseline and (default "
+                    "configuration) the extra_configs legs: everything beyond the headline figure")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed (losses, model state after the "
+                    "update) as DIR/<name>.npy, float32 / float64, for output-by-output comparison of two builds")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
     ap.add_argument("--cpu-iters", type=int, default=5)       # ~13 s of CPU work at 2D config 1 (9.4 vol/s on 16 cores)
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra_configs legs (config 3 = 3D bf16, and the 2D fp32 parity mode) of the default run")
+    ap.add_argument("--no-extra", action="store_true", help="(--full) skip the extra_configs legs (config 3 = 3D bf16, and the 2D fp32 parity mode) of the default run")
     ap.add_argument("--extra-steps", type=int, default=10)
     ap.add_argument("--stage", action="store_true", help="with --host-inputs: ChapStep.stage() the next batch beside the running iteration (what chap_amd's train() does)")
     ap.add_argument("--host-inputs", choices=["pinned", "pageable"], default=None, help="hand every step HOST tensors (the reference's loader yields CPU batches): the "
@@ -409,6 +418,30 @@ def time_steps(run, steps, warmup, dist, dev):
     return dt, out
 
 
+DUMP_BUDGET_BYTES = 64 << 20        # the largest dump, the 3D DualDecoder3d's state, is 47 MB
+
+
+def dump_outputs(path, out, model):
+    """What a caller of the timed step holds after the last one: its returned losses and the model's state_dict (parameters after
+    the SGD update, BatchNorm statistics), as float32 (float64 for integer buffers)."""
+    arrays = {}
+    for k, v in out.items():
+        if isinstance(v, (list, tuple)):
+            for i, t in enumerate(v):
+                arrays["%s.%d" % (k, i)] = t
+        elif torch.is_tensor(v):
+            arrays[k] = v
+    for k, v in model.state_dict().items():
+        arrays["model." + k] = v
+    arrays = {k: v.detach().cpu().numpy().astype(np.float32 if v.is_floating_point() else np.float64) for k, v in arrays.items()}
+    if sum(a.nbytes for a in arrays.values()) > DUMP_BUDGET_BYTES:
+        raise SystemExit("--dump-outputs: %.1f MB of outputs, more than the 64 MB a dump may hold" % (sum(a.nbytes for a in arrays.values()) / 2**20))
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    log("dumped %d arrays (%.1f MB) to %s" % (len(arrays), sum(a.nbytes for a in arrays.values()) / 2**20, path))
+
+
 def extra_config(cfg, dtype_name, B, sp, K, steps, dev):
     """One more configuration on the same line (`extra_configs`): the same iteration, captured and timed the same way."""
     model, step, dtype = build_step(cfg, dtype_name, B, sp, K, {}, 1, dev)
@@ -467,6 +500,8 @@ def main():
     for kv in args.set:
         k, v = kv.split("=", 1)
         extra[k] = json.loads(v) if v[:1] in "0123456789-[{tfn\"" else v
+    np.random.seed(1337)                # the host-side draws of the iteration (BCP box offsets): the same inputs on every run
+    random.seed(1337)
     model, step, dtype = build_step(args.config, args.dtype, B, sp, args.vat_iters, extra, world, dev)
     if dist is not None:
         from chap_amd.parallel import DataParallelSync
@@ -504,35 +539,38 @@ def main():
         dist.barrier()
         dist.destroy_process_group()        # before the roofline probes: they capture graphs, and the RCCL watchdog polls events
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, out, model)
         K = args.vat_iters
-        bytes_per_vol, flops_per_vol = work_per_volume(args.config, args.dtype, sp, K)
-        roof = dominant_kernel_roofline_3d(dtype, B // 2, sp) if d3 else dominant_kernel_roofline(model, dtype, B // 2, H)
-        roof["top_kernel"] = top_kernel_roofline(dtype, B // 2, args.config, sp)
-        roof["iteration_hbm_frac_vs_ideal_fusion"] = round(vps / world * bytes_per_vol / 1e9 / HBM_PEAK_GBS, 4)
-        roof["iteration_tflops"] = round(vps / world * flops_per_vol / 1e12, 2)
         line = {"metric": "training volumes/sec (%s)" % ("3D 112x112x80 bs4" if d3 else "2D 256^2 bs24"), "value": round(vps, 2), "unit": "volumes/s", "n_gpus": world,
                 "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
                 "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype,
                 "data": "synthetic" if not args.host_inputs else "synthetic, handed over as %s HOST tensors every step (PCIe-inclusive: not the headline value)" % args.host_inputs,
                 "config": {"workload": workload_name(args.config, B, sp, K),
                            "global_batch": B * world, "parallelism": "dp%d" % world, "hip_graph": use_graph, "losses_finite": finite,
-                           "grad_exchange": None if world == 1 and not force_dp else ("rccl all-reduce, bucket 0 overlapped with the VAT chain" if args.dp_overlap else "rccl all-reduce of the folded buckets")},
-                "roofline": roof}
+                           "grad_exchange": None if world == 1 and not force_dp else ("rccl all-reduce, bucket 0 overlapped with the VAT chain" if args.dp_overlap else "rccl all-reduce of the folded buckets")}}
         if args.rehearse_one_gpu:
             line["rehearsal"] = "%d ranks on ONE GPU, gradients through host memory (gloo): exercises the multi-rank path, NOT a scaling measurement" % world
-        # the other single-GPU configurations on the driver's line (default run only): BASELINE config 3 (3D, bf16) and the fp32 parity mode
-        default_run = world == 1 and not force_dp and not d3 and args.dtype == "bf16" and not args.batch and H == 256 and args.vat_iters == 1 and use_graph and not extra
-        if default_run and not args.no_extra:
-            del step, model
-            torch.cuda.empty_cache()
-            line["extra_configs"] = []
-            for cfg_, dt_, B_, sp_ in (("3d", "bf16", 4, (112, 112, 80)), ("2d", "fp32", 24, (256, 256))):
-                log("extra config: %s %s" % (cfg_, dt_))
-                line["extra_configs"].append(extra_config(cfg_, dt_, B_, sp_, 1, args.extra_steps, dev))
-        if not args.no_cpu_baseline and world == 1:
-            line["cpu_baseline"] = cpu_baseline(args, B, sp)
-        else:
-            line["cpu_baseline"] = None
+        if args.full:           # beyond the headline figure: measured after the timed steps, in runs of their own
+            bytes_per_vol, flops_per_vol = work_per_volume(args.config, args.dtype, sp, K)
+            roof = dominant_kernel_roofline_3d(dtype, B // 2, sp) if d3 else dominant_kernel_roofline(model, dtype, B // 2, H)
+            roof["top_kernel"] = top_kernel_roofline(dtype, B // 2, args.config, sp)
+            roof["iteration_hbm_frac_vs_ideal_fusion"] = round(vps / world * bytes_per_vol / 1e9 / HBM_PEAK_GBS, 4)
+            roof["iteration_tflops"] = round(vps / world * flops_per_vol / 1e12, 2)
+            line["roofline"] = roof
+            # the other single-GPU configurations on the driver's line (default run only): BASELINE config 3 (3D, bf16) and the fp32 parity mode
+            default_run = world == 1 and not force_dp and not d3 and args.dtype == "bf16" and not args.batch and H == 256 and args.vat_iters == 1 and use_graph and not extra
+            if default_run and not args.no_extra:
+                del step, model
+                torch.cuda.empty_cache()
+                line["extra_configs"] = []
+                for cfg_, dt_, B_, sp_ in (("3d", "bf16", 4, (112, 112, 80)), ("2d", "fp32", 24, (256, 256))):
+                    log("extra config: %s %s" % (cfg_, dt_))
+                    line["extra_configs"].append(extra_config(cfg_, dt_, B_, sp_, 1, args.extra_steps, dev))
+            if not args.no_cpu_baseline and world == 1:
+                line["cpu_baseline"] = cpu_baseline(args, B, sp)
+            else:
+                line["cpu_baseline"] = None
         os.write(real_stdout, (json.dumps(line) + "\n").encode())
 
 

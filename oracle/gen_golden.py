@@ -9,6 +9,7 @@ inputs, outputs, gradients and state-dict key/shape lists.
 
     PYTHONDONTWRITEBYTECODE=1 python oracle/gen_golden.py
 """
+import math
 import os
 import sys
 import types
@@ -80,6 +81,13 @@ def _np(t):
 def _checks(named):
     """per-tensor (sum, abs-sum) table, float64."""
     return np.array([[float(t.double().sum()), float(t.double().abs().sum())] for _, t in named], dtype=np.float64)
+
+
+def _exact_checks(named):
+    """per-tensor (sum, abs-sum) table, float64, correctly rounded (math.fsum): the same on every machine, whatever order a
+    vectorised or threaded reduction would add in -- for checks compared bit for bit."""
+    flat = [t.detach().double().reshape(-1).tolist() for _, t in named]
+    return np.array([[math.fsum(v), math.fsum(map(abs, v))] for v in flat], dtype=np.float64)
 
 
 def run_case(model, x, cot_seed, train, dtype=torch.float32):
@@ -178,7 +186,7 @@ def gen_2d(ref):
     md = ref["DualDecoder"](1, 4, {"decoder_type": "mcnet"})
     np.savez_compressed(os.path.join(OUT, "dualdecoder2d_init1337.npz"),
                         keys=np.array(list(md.state_dict().keys())),
-                        checks=_checks(list(md.state_dict().items())))
+                        checks=_exact_checks(list(md.state_dict().items())))
 
 
 def gen_unet_feats(ref):
@@ -285,7 +293,7 @@ def gen_3d(ref):
     md = ref["DualDecoder3d"](n_channels=1, n_classes=2, normalization="batchnorm", has_dropout=True)
     np.savez_compressed(os.path.join(OUT, "dualdecoder3d_init1337.npz"),
                         keys=np.array(list(md.state_dict().keys())),
-                        checks=_checks(list(md.state_dict().items())))
+                        checks=_exact_checks(list(md.state_dict().items())))
 
 
 def gen_3d_full(ref):

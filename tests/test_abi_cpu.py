@@ -3,6 +3,7 @@ exports every symbol include/chap_hip.h declares (no compute calls), ctypes stru
 header (via a compiled sizeof probe), and the drop-in modules reproduce the reference's state-dict
 keys/shapes and default initialisation."""
 import ctypes
+import math
 import os
 import re
 import subprocess
@@ -69,6 +70,13 @@ def test_errors_are_reported_not_swallowed():
         _lib.call("chap_pack_weights", p, 0)
 
 
+def _exact_checks(sd):
+    """(sum, abs-sum) of every tensor, correctly rounded (math.fsum, as oracle/gen_golden.py stores them): bit for bit the same on
+    every machine -- torch's float64 sum is not, its order follows the host's vector width and thread count."""
+    flat = [t.detach().double().reshape(-1).tolist() for t in sd.values()]
+    return np.array([[math.fsum(v), math.fsum(map(abs, v))] for v in flat], dtype=np.float64)
+
+
 def test_state_dict_contract_2d(golden_dir):
     from chap_amd.networks import DualDecoder, UNet
     g = np.load(os.path.join(golden_dir, "dualdecoder2d_64.npz"))
@@ -82,7 +90,7 @@ def test_state_dict_contract_2d(golden_dir):
     gi = np.load(os.path.join(golden_dir, "dualdecoder2d_init1337.npz"))
     torch.manual_seed(1337)
     md = DualDecoder(1, 4, {"decoder_type": "mcnet"})
-    chk = np.array([[float(t.double().sum()), float(t.double().abs().sum())] for t in md.state_dict().values()])
+    chk = _exact_checks(md.state_dict())
     np.testing.assert_allclose(chk, gi["checks"], rtol=0, atol=0)
     u = UNet(1, 4)
     assert list(u.state_dict().keys()) == list(np.load(os.path.join(golden_dir, "unet2d_32.npz"))["keys"])
@@ -99,7 +107,7 @@ def test_state_dict_contract_3d(golden_dir):
     gi = np.load(os.path.join(golden_dir, "dualdecoder3d_init1337.npz"))
     torch.manual_seed(1337)
     md = DualDecoder3d(n_channels=1, n_classes=2, normalization="batchnorm", has_dropout=True)
-    chk = np.array([[float(t.double().sum()), float(t.double().abs().sum())] for t in md.state_dict().values()])
+    chk = _exact_checks(md.state_dict())
     np.testing.assert_allclose(chk, gi["checks"], rtol=0, atol=0)
     v = VNet(n_channels=1, n_classes=2, normalization="batchnorm")
     assert list(v.state_dict().keys()) == list(np.load(os.path.join(golden_dir, "vnet_16.npz"))["keys"])

@@ -4,19 +4,19 @@
 set -o pipefail
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r02; mkdir -p $O; cd /tmp; export TMPDIR=/tmp
 # 1. bench lines: BASELINE config 1 (default), fp32 mode, 3D 112x112x80, 3D 112^3 extra row
-python3 $R/bench.py > $O/bench2d_bf16.json 2> $O/bench2d_bf16.err
-python3 $R/bench.py --dtype fp32 --no-cpu-baseline > $O/bench2d_fp32.json 2> $O/bench2d_fp32.err
-python3 $R/bench.py --config 3d --steps 10 --warmup 3 > $O/bench3d_bf16.json 2> $O/bench3d_bf16.err
-python3 $R/bench.py --config 3d --dtype fp32 --steps 5 --warmup 2 --no-cpu-baseline > $O/bench3d_fp32.json 2> $O/bench3d_fp32.err
-python3 $R/bench.py --config 3d --size3d 112 112 112 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench3d_112cube_bf16.json 2> $O/bench3d_112cube.err
-python3 $R/bench.py --config 3d --vat-iters 2 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench3d_k2_bf16.json 2> $O/bench3d_k2.err
-CHAP_FORCE_DP=1 python3 $R/bench.py --steps 30 --warmup 5 --no-cpu-baseline > $O/bench2d_dp1_fold.json 2> $O/bench2d_dp1_fold.err
-CHAP_FORCE_DP=1 python3 $R/bench.py --steps 30 --warmup 5 --no-cpu-baseline --dp-overlap > $O/bench2d_dp1_overlap.json 2> $O/bench2d_dp1_overlap.err
+python3 $R/bench.py --full > $O/bench2d_bf16.json 2> $O/bench2d_bf16.err
+python3 $R/bench.py --full --dtype fp32 --no-cpu-baseline > $O/bench2d_fp32.json 2> $O/bench2d_fp32.err
+python3 $R/bench.py --full --config 3d --steps 10 --warmup 3 > $O/bench3d_bf16.json 2> $O/bench3d_bf16.err
+python3 $R/bench.py --full --config 3d --dtype fp32 --steps 5 --warmup 2 --no-cpu-baseline > $O/bench3d_fp32.json 2> $O/bench3d_fp32.err
+python3 $R/bench.py --full --config 3d --size3d 112 112 112 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench3d_112cube_bf16.json 2> $O/bench3d_112cube.err
+python3 $R/bench.py --full --config 3d --vat-iters 2 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench3d_k2_bf16.json 2> $O/bench3d_k2.err
+CHAP_FORCE_DP=1 python3 $R/bench.py --full --steps 30 --warmup 5 --no-cpu-baseline > $O/bench2d_dp1_fold.json 2> $O/bench2d_dp1_fold.err
+CHAP_FORCE_DP=1 python3 $R/bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --dp-overlap > $O/bench2d_dp1_overlap.json 2> $O/bench2d_dp1_overlap.err
 echo "bench lines done"
 # 2. kernel-trace stats of the two bench configurations
 for c in 2d 3d; do
   rm -rf $O/ks$c
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks$c -- python3 $R/bench.py --config $c --no-cpu-baseline --steps 10 --warmup 3 > $O/ks$c.json 2> $O/ks$c.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks$c -- python3 $R/bench.py --full --config $c --no-cpu-baseline --steps 10 --warmup 3 > $O/ks$c.json 2> $O/ks$c.err
   cp $(find $O/ks$c -name "*kernel_stats.csv" | head -1) $O/r02_bench${c}_kernel_stats.csv
 done
 echo "kernel stats done"

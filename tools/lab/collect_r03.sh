@@ -6,20 +6,20 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r03; mkdir -p $O; cd /tmp; export TMPDIR=/tm
 PARTS=${*:-bench stats shapes pmc}
 has() { [[ " $PARTS " == *" $1 "* ]]; }
 if has bench; then
-python3 $R/bench.py > $O/r03_bench2d_bf16.json 2> $O/bench2d_bf16.err
-python3 $R/bench.py --config 3d --steps 20 --warmup 5 > $O/r03_bench3d_bf16.json 2> $O/bench3d_bf16.err
-python3 $R/bench.py --dtype fp32 --no-cpu-baseline --no-extra > $O/r03_bench2d_fp32.json 2> $O/bench2d_fp32.err
-python3 $R/bench.py --config 3d --dtype fp32 --steps 5 --warmup 2 --no-cpu-baseline > $O/r03_bench3d_fp32.json 2> $O/bench3d_fp32.err
-python3 $R/bench.py --config 3d --size3d 112 112 112 --steps 10 --warmup 3 --no-cpu-baseline > $O/r03_bench3d_112cube_bf16.json 2> $O/bench3d_112cube.err
-python3 $R/bench.py --config 3d --vat-iters 2 --steps 10 --warmup 3 --no-cpu-baseline > $O/r03_bench3d_k2_bf16.json 2> $O/bench3d_k2.err
-CHAP_GROUP=0 python3 $R/bench.py --no-cpu-baseline --no-extra > $O/r03_bench2d_bf16_nogroup.json 2> $O/bench2d_nogroup.err
-CHAP_GROUP=0 python3 $R/bench.py --config 3d --steps 20 --warmup 5 --no-cpu-baseline > $O/r03_bench3d_bf16_nogroup.json 2> $O/bench3d_nogroup.err
+python3 $R/bench.py --full > $O/r03_bench2d_bf16.json 2> $O/bench2d_bf16.err
+python3 $R/bench.py --full --config 3d --steps 20 --warmup 5 > $O/r03_bench3d_bf16.json 2> $O/bench3d_bf16.err
+python3 $R/bench.py --full --dtype fp32 --no-cpu-baseline --no-extra > $O/r03_bench2d_fp32.json 2> $O/bench2d_fp32.err
+python3 $R/bench.py --full --config 3d --dtype fp32 --steps 5 --warmup 2 --no-cpu-baseline > $O/r03_bench3d_fp32.json 2> $O/bench3d_fp32.err
+python3 $R/bench.py --full --config 3d --size3d 112 112 112 --steps 10 --warmup 3 --no-cpu-baseline > $O/r03_bench3d_112cube_bf16.json 2> $O/bench3d_112cube.err
+python3 $R/bench.py --full --config 3d --vat-iters 2 --steps 10 --warmup 3 --no-cpu-baseline > $O/r03_bench3d_k2_bf16.json 2> $O/bench3d_k2.err
+CHAP_GROUP=0 python3 $R/bench.py --full --no-cpu-baseline --no-extra > $O/r03_bench2d_bf16_nogroup.json 2> $O/bench2d_nogroup.err
+CHAP_GROUP=0 python3 $R/bench.py --full --config 3d --steps 20 --warmup 5 --no-cpu-baseline > $O/r03_bench3d_bf16_nogroup.json 2> $O/bench3d_nogroup.err
 echo "bench lines done"
 fi
 if has stats; then
 for c in 2d 3d; do
   rm -rf $O/ks$c
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks$c -- python3 $R/bench.py --config $c --no-cpu-baseline --no-extra --steps 10 --warmup 3 > $O/ks$c.json 2> $O/ks$c.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks$c -- python3 $R/bench.py --full --config $c --no-cpu-baseline --no-extra --steps 10 --warmup 3 > $O/ks$c.json 2> $O/ks$c.err
   cp $(find $O/ks$c -name "*kernel_stats.csv" | head -1) $O/r03_bench${c}_kernel_stats.csv
 done
 echo "kernel stats done"

@@ -3,7 +3,7 @@
 set -o pipefail
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/kp; mkdir -p $O; cd $R
 b() { tag=$1; shift
-  env "$@" python3 bench.py --no-cpu-baseline --no-extra --steps 30 --warmup 5 > $O/$tag.json 2> $O/$tag.err || { echo "$tag FAILED"; return 0; }
+  env "$@" python3 bench.py --full --no-cpu-baseline --no-extra --steps 30 --warmup 5 > $O/$tag.json 2> $O/$tag.err || { echo "$tag FAILED"; return 0; }
   python3 - $tag $O/$tag.json <<'P'
 import json,sys
 d=json.load(open(sys.argv[2])); print("%-16s %.3f ms  %.1f vol/s   top_kernel %.2f us frac %.4f"%(sys.argv[1], d["ms_per_step"], d["value"], d["roofline"]["top_kernel"]["avg_launch_us"], d["roofline"]["top_kernel"]["frac"]))

@@ -12,5 +12,5 @@ done
 done
 cd $R
 for c in 2d 3d; do CHAP_LIBPATH=tools/lab/libchap_hip_lab.so python3 tools/timeline_untraced.py --config $c --out $O/r04_timeline_untraced_$c.json > $O/timeline_$c.log 2>&1 || exit 1; done
-python3 bench.py > $O/r04_bench2d_bf16.json 2> $O/bench2d_bf16.err &&
-python3 bench.py --config 3d --steps 20 --warmup 5 > $O/r04_bench3d_bf16.json 2> $O/bench3d_bf16.err
+python3 bench.py --full > $O/r04_bench2d_bf16.json 2> $O/bench2d_bf16.err &&
+python3 bench.py --full --config 3d --steps 20 --warmup 5 > $O/r04_bench3d_bf16.json 2> $O/bench3d_bf16.err
