@@ -189,6 +189,21 @@ class DiffMaskParams(C.Structure):
                 ("N", _i32), ("H", _i32), ("W", _i32), ("scale", _i32), ("topk", _f32)]
 
 
+class MetricResult(C.Structure):
+    _fields_ = [("n_a", _i64), ("n_b", _i64), ("n_ab", _i64), ("n_ab_s", _i64), ("n_ba_s", _i64), ("q_lo", _i64), ("q_hi", _i64),
+                ("sum_ab", C.c_double), ("sum_ba", C.c_double), ("max2_ab", C.c_double), ("max2_ba", C.c_double),
+                ("v2_lo", C.c_double), ("v2_hi", C.c_double)]
+
+
+class MetricsParams(C.Structure):
+    _fields_ = [("a", _vp), ("b", _vp), ("a_i64", _i32), ("b_i64", _i32), ("classes", _vp), ("K", _i32), ("binary", _i32),
+                ("ndim", _i32), ("D", _i32), ("H", _i32), ("W", _i32), ("distances", _i32), ("spacing", C.c_double * 3),
+                ("border_a", _vp), ("border_b", _vp), ("dist", _vp), ("results", _vp), ("ws", _vp)]
+
+
+METRICS_MAX_AXIS = 4096                        # CHAP_METRICS_MAX_AXIS
+
+
 class GradSimParams(C.Structure):
     _fields_ = [("gl", _vp), ("gu", _vp), ("score", _vp), ("C", _i32), ("K", _i32), ("ema", _f32)]
 
@@ -211,10 +226,10 @@ _SIGS = {  # name -> (restype, params struct or None)
     "chap_box_mix": BoxMixParams, "chap_box_mask": BoxMaskParams, "chap_largest_cc": LccParams,
     "chap_diff_mask": DiffMaskParams, "chap_sgd_step": SgdParams,
     "chap_sample_channel_sum": SampleChanSumParams, "chap_channel_drop": ChannelDropParams,
-    "chap_fold_perturbed": FoldParams, "chap_grad_sim": GradSimParams,
+    "chap_fold_perturbed": FoldParams, "chap_grad_sim": GradSimParams, "chap_metrics": MetricsParams,
 }
 _SIZE_FNS = {"chap_pack_size": PackParams, "chap_conv_c1_bwd_ws": ConvC1BwdParams, "chap_wgrad_ws": WgradParams,
-             "chap_lcc_ws": LccParams}
+             "chap_lcc_ws": LccParams, "chap_metrics_ws": MetricsParams}
 
 _lib = None
 

@@ -6,14 +6,15 @@ window, softmax score accumulation, count normalisation, argmax).  Same names, a
 differences are internal: slices / patches go through the network in batches, the ensemble + softmax + argmax and
 the score-map accumulation run in HIP kernels (`chap_ensemble_argmax`, `chap_window_accumulate/finalize`) and
 nothing is copied to the host per slice / per patch.  The nearest-neighbour zoom is an index plan that reproduces
-scipy.ndimage.zoom(order=0) bit for bit (including its edge quirk) and runs on the device.
+scipy.ndimage.zoom(order=0) bit for bit (including its edge quirk) and runs on the device.  Without medpy, the Dice / HD95 /
+ASD of the predictions come from chap_amd.metrics (HIP kernels, one launch chain for all classes of a volume).
 """
 import math
 
 import numpy as np
 import torch
 
-from . import ops
+from . import metrics, ops
 
 
 _ZOOM_PLANS = {}
@@ -49,6 +50,14 @@ def zoom0(t, factors):
     return torch.where(mask, out, torch.zeros((), dtype=t.dtype, device=t.device))
 
 
+def _have_medpy():
+    try:
+        from medpy import metric  # noqa: F401
+        return True
+    except ImportError:
+        return False
+
+
 def _dice_hd95(pred, gt):
     """calculate_metric_percase (val_2D.py:43-51): Dice and HD95 of two binary masks (medpy when installed)."""
     pred = (pred > 0)
@@ -64,8 +73,8 @@ def _dice_hd95(pred, gt):
     return 0, 0
 
 
-def predict_volume(image, net, patch_size=(256, 256), model_type="logit_ensemble", device="cuda:0", batch=32):
-    """image: numpy [S, X, Y] -> prediction uint8 [S, X, Y] (the loop body of test_single_volume, all slices batched)."""
+def predict_volume_device(image, net, patch_size=(256, 256), model_type="logit_ensemble", device="cuda:0", batch=32):
+    """image: numpy [S, X, Y] -> prediction uint8 [S, X, Y] on the device (the loop body of test_single_volume, all slices batched)."""
     S, x, y = image.shape
     vol = torch.from_numpy(np.ascontiguousarray(image)).to(device)
     zoomed = zoom0(vol, (patch_size[0] / x, patch_size[1] / y))          # the reference's per-slice zoom(order=0), on the device
@@ -82,8 +91,12 @@ def predict_volume(image, net, patch_size=(256, 256), model_type="logit_ensemble
             mode = model_type if o2 is not None else "model1"
             label, _ = ops.ensemble_argmax(o1.contiguous(), None if o2 is None else o2.contiguous(), mode)
             out[s0:s0 + batch] = label
-    pred = zoom0(out, (x / patch_size[0], y / patch_size[1]))
-    return pred.cpu().numpy()
+    return zoom0(out, (x / patch_size[0], y / patch_size[1]))
+
+
+def predict_volume(image, net, patch_size=(256, 256), model_type="logit_ensemble", device="cuda:0", batch=32):
+    """image: numpy [S, X, Y] -> prediction uint8 [S, X, Y] (numpy)."""
+    return predict_volume_device(image, net, patch_size, model_type, device, batch).cpu().numpy()
 
 
 def test_single_volume(image, label, net, classes, patch_size=[256, 256], model_type="unet", device="cuda:0", batch=32):
@@ -93,11 +106,32 @@ def test_single_volume(image, label, net, classes, patch_size=[256, 256], model_
     image, label = image.squeeze(0).cpu().detach().numpy(), label.squeeze(0).cpu().detach().numpy()
     if model_type not in ops.ENSEMBLE_MODES:
         raise ValueError("model_type must be one of %s" % sorted(ops.ENSEMBLE_MODES))
+    if not _have_medpy():
+        # every class from the device-resident prediction, one chap_metrics chain (chap_amd.metrics), _dice_hd95's guards
+        prediction = predict_volume_device(image, net, tuple(patch_size), model_type, device, batch)
+        with torch.cuda.device(prediction.device):
+            r = metrics.per_class(prediction, label, list(range(1, classes)))
+        return [(0, 0) if r["n_a"][k] == 0 else (float(r["dc"][k]), float(r["hd95"][k])) for k in range(classes - 1)]
     prediction = predict_volume(image, net, tuple(patch_size), model_type, device, batch).astype(label.dtype)
     metric_list = []
     for i in range(1, classes):
         metric_list.append(_dice_hd95(prediction == i, label == i))
     return metric_list
+
+
+def calculate_metric_percase(pred, gt):
+    """test_3D_util.py:147-152: [dc, |ravd|, hd95, asd] of two binary masks (medpy when installed, else one chap_metrics chain).
+    Raises where medpy does: RuntimeError when gt is empty (ravd) or pred is empty (hd95)."""
+    if _have_medpy():
+        from medpy import metric
+        return np.array([metric.binary.dc(pred, gt), abs(metric.binary.ravd(pred, gt)), metric.binary.hd95(pred, gt),
+                         metric.binary.asd(pred, gt)])
+    s = metrics.binary_all(pred, gt)
+    if s["n_b"] == 0:
+        raise RuntimeError("The second supplied array does not contain any binary object.")
+    if s["n_a"] == 0:
+        raise RuntimeError("The first supplied array does not contain any binary object.")
+    return np.array([s["dc"], abs(s["ravd"]), s["hd95"], s["asd"]])
 
 
 def test_single_case(net, image, stride_xy, stride_z, patch_size, num_classes=1, batch=4, device="cuda:0", return_score=False):

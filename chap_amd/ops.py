@@ -503,3 +503,28 @@ def window_finalize(score, cnt):
     p.score, p.cnt, p.label, p.C, p.P = score.data_ptr(), cnt.data_ptr(), label.data_ptr(), score.shape[0], cnt.numel()
     L.call("chap_window_finalize", p, _stream())
     return label
+
+
+def metrics(a, b, classes, *, ndim, spacing=(1.0, 1.0, 1.0), binary=False, distances=True):
+    """chap_metrics: a, b contiguous uint8 / int64 device tensors of one shape [D, H, W] (ndim 2: D == 1); classes: device int64 [K]
+    (None when binary).  spacing: per axis (D, H, W).  Returns (results uint8 [K * sizeof(chap_metric_result)] on the device,
+    border_a, border_b uint8 [D, H, W], dist fp64 [K, 2, D, H, W] or None)."""
+    D, H, W = a.shape
+    K = 1 if binary else classes.numel()
+    p = L.MetricsParams()
+    p.a, p.b = a.data_ptr(), b.data_ptr()
+    p.a_i64, p.b_i64 = int(a.dtype == torch.int64), int(b.dtype == torch.int64)
+    p.classes, p.K, p.binary = (None if binary else classes.data_ptr()), K, int(binary)
+    p.ndim, p.D, p.H, p.W, p.distances = ndim, D, H, W, int(distances)
+    p.spacing[0], p.spacing[1], p.spacing[2] = (float(s) for s in spacing)
+    border_a = L.hold_empty((D, H, W), dtype=torch.uint8, device=a.device)
+    border_b = L.hold_empty((D, H, W), dtype=torch.uint8, device=a.device)
+    results = L.hold_empty(K * L.C.sizeof(L.MetricResult), dtype=torch.uint8, device=a.device)
+    p.border_a, p.border_b, p.results = border_a.data_ptr(), border_b.data_ptr(), results.data_ptr()
+    dist = None
+    if distances:
+        dist = L.hold_empty((K, 2, D, H, W), dtype=torch.float64, device=a.device)
+        ws = L.hold_empty(L.size_of("chap_metrics_ws", p), dtype=torch.uint8, device=a.device)
+        p.dist, p.ws = dist.data_ptr(), ws.data_ptr()
+    L.call("chap_metrics", p, _stream())
+    return results, border_a, border_b, dist

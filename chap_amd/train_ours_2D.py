@@ -89,13 +89,14 @@ def train(args, snapshot_path):
             metric = sum(np.array(test_single_volume(im, lb, model, classes=a["num_classes"], patch_size=a["image_size"],
                                                      model_type="logit_ensemble", device=device)) for im, lb in val) / len(val)
             performance = float(np.mean(metric, axis=0)[0])
+            mean_hd95 = float(np.mean(metric, axis=0)[1])
             torch.save(model.state_dict(), os.path.join(snapshot_path, "latest.pth"))
             if performance > best:
                 best = performance
                 torch.save(model.state_dict(), os.path.join(snapshot_path, "{}_best_model.pth".format(a["model"])))
                 with open(os.path.join(snapshot_path, "val.csv"), "a", newline="") as f:
                     csv.writer(f).writerow([time.strftime("%Y-%m-%d %H:%M:%S"), it, round(best, 4)])
-            log.info("iteration %d : model1_mean_dice : %f" % (it, performance))
+            log.info("iteration %d : model1_mean_dice : %f model1_mean_hd95 : %f" % (it, performance, mean_hd95))      # :453-454
             model.train()
         if it >= a["max_iterations"]:
             break

@@ -42,6 +42,7 @@
  *      stream: +15-22 % step time), the "lazy gradient" chap_bgrad_t of chap_wgrad (+0.8 / +2.7 %), the deferred multi-layer slab reduction
  *      (+-0 / +1 %); measurements in DESIGN.md section 5.  chap_conv_params.out2 / out2_from (a concat layer's input gradient as two dense
  *      tensors).
+ *      Additive, no version change: chap_metrics / chap_metrics_ws (segmentation metrics, new structs only).
  */
 #ifndef CHAP_HIP_H
 #define CHAP_HIP_H
@@ -385,6 +386,44 @@ typedef struct { const float* logits; const int32_t* origins; float* score; floa
 int chap_window_accumulate(const chap_window_acc_params* p, void* stream);
 typedef struct { float* score; const float* cnt; uint8_t* label; int32_t C; int64_t P; } chap_window_fin_params;
 int chap_window_finalize(const chap_window_fin_params* p, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Segmentation metrics: what medpy.metric.binary dc / jc / ravd / hd / hd95 / asd / assd need, for K classes of
+ * one pair of maps in one launch chain (callers: val_2D.py:43-51, test_2D_fully.py:37-51, test_3D_util.py:82-88,147-152).
+ *   A = result (a), B = reference (b): maps [D][H][W] of uint8 or int64 (a_i64 / b_i64); ndim 3: 6-neighbourhood, ndim 2 (D == 1):
+ *   4-neighbourhood in the plane.  binary = 1: A and B are "value != 0" (K == 1, classes unused); binary = 0: class k is
+ *   "value == classes[k]" (classes: device int64 [K], distinct values, K <= 255).
+ *   border(X) = X minus its erosion by the cross footprint, voxels outside the array counted as "out" (scipy binary_erosion,
+ *   border_value 0).  border_a / border_b (out, uint8 [D][H][W]): k + 1 at the border voxels of class k, else 0.
+ *   distances = 0: counts only (n_a, n_b, n_ab; dist and ws unused).  distances = 1, in addition:
+ *   dist (out, fp64 [K][2][D][H][W]): exact squared Euclidean distance transform with the per-axis spacing (D, H, W), [k][0] to the
+ *   nearest border voxel of B (sampled at border(A): sds(A, B)), [k][1] to border(A); +inf when there is none.  Separable: a 1D
+ *   two-sweep pass along W, then f(i) = min_j g(j) + ((i - j) * s)^2 along H and D; every axis <= CHAP_METRICS_MAX_AXIS.  At unit
+ *   spacing every value is an integer and bitwise that of scipy.ndimage.distance_transform_edt squared.
+ *   results (out, device [K]): counts, fixed-order sums, maxima and the two squared order statistics HD95 interpolates between (ranks
+ *   floor((n - 1) * 0.95) and the next, capped at n - 1, of the union of both directions' n samples; -1 / NaN when A or B is empty).
+ *   No float atomics: bitwise reproducible.  ws: chap_metrics_ws() bytes. */
+#define CHAP_METRICS_MAX_AXIS 4096
+typedef struct {
+    int64_t n_a, n_b, n_ab;        /* |A|, |B|, |A & B|                                                              */
+    int64_t n_ab_s, n_ba_s;        /* samples of sds(A, B) (= |border(A)|) and of sds(B, A) (= |border(B)|)          */
+    int64_t q_lo, q_hi;            /* 0-based ascending ranks of the HD95 order statistics in the union, or -1       */
+    double sum_ab, sum_ba;         /* sum of sqrt(d^2) over the samples of each direction (fixed order)              */
+    double max2_ab, max2_ba;       /* largest d^2 of each direction                                                  */
+    double v2_lo, v2_hi;           /* the squared order statistics of ranks q_lo, q_hi (NaN when q_lo == -1)         */
+} chap_metric_result;
+typedef struct {
+    const void* a; const void* b; int32_t a_i64, b_i64;
+    const int64_t* classes; int32_t K, binary;
+    int32_t ndim, D, H, W, distances;
+    double spacing[3];             /* D, H, W axes; spacing[0] unused when ndim == 2                                  */
+    uint8_t* border_a; uint8_t* border_b;
+    double* dist;
+    chap_metric_result* results;
+    void* ws;
+} chap_metrics_params;
+size_t chap_metrics_ws(const chap_metrics_params* p);
+int    chap_metrics(const chap_metrics_params* p, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Channel-level perturbation: FilterDropout.perform_dropout (FilterDropout.py:45-89) as two kernels.
