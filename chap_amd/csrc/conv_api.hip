@@ -162,7 +162,8 @@ extern "C" int chap_conv_fwd(const chap_conv_params* p, void* stream) {
     // 34.1 -> 29.1 us, 32->16 32.0 -> 25.1, 32->64 at 128 x 128 20.6 -> 17.9, 16->32 at 128 x 128 14.9 -> 13.0; the 16->16 layer with BatchNorm prologue and
     // statistics 20.8 -> 20.5 (it is VALU-bound in its staging, not short of loads in flight), 32->32 with statistics 14.7 -> 15.3.  Whole 2D iteration, three
     // A/B pairs: 6.451 -> 6.406 ms.  Outputs are bit-identical to conv_fwd_kernel's.
-    if (p->dtype == CHAP_BF16 && geom == 1 && p->out_mode == 0 && !p->out_planar && !p->out_f32 && (p->Cout & 15) == 0 && p->Cout <= 64 && p->combine == 0 &&
+    // (D == 1: the kernel walks N images of H x W; dims = 2 with D > 1 -- N*D slices -- takes the generic kernel)
+    if (p->dtype == CHAP_BF16 && geom == 1 && p->D == 1 && p->out_mode == 0 && !p->out_planar && !p->out_f32 && (p->Cout & 15) == 0 && p->Cout <= 64 && p->combine == 0 &&
         Ck == b.KC && (p->nsrc == 1 || (b.KC == 32 && p->src[0].C == 16 && p->src[1].C == 16))) {
         const char* ew = getenv("CHAP_CONV_WP");
         const long wp_min = ew ? atol(ew) : 1;

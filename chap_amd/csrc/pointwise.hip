@@ -692,8 +692,10 @@ __device__ __forceinline__ void act_bwd_kernel(const chap_act_bwd_params& P) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             float a = s0[j], b = s1[j];
-            // inside a 16-lane row: DPP rotations (C8 is wave-uniform); across rows: two shuffles
-            if (C8 == 2) { a = row16_stride_sum<2>(a); b = row16_stride_sum<2>(b); }
+            // inside a 16-lane row: DPP rotations (C8 is wave-uniform); across rows: two shuffles.  C8 == 1 (C = 8): all 16 lanes of a row hold the
+            // same channels -- the whole row
+            if (C8 == 1) { a = row16_sum(a); b = row16_sum(b); }
+            else if (C8 == 2) { a = row16_stride_sum<2>(a); b = row16_stride_sum<2>(b); }
             else if (C8 == 4) { a = row16_stride_sum<4>(a); b = row16_stride_sum<4>(b); }
             else if (C8 == 8) { a = row16_stride_sum<8>(a); b = row16_stride_sum<8>(b); }
             for (int o = (C8 > 16 ? C8 : 16); o < 64; o <<= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); }

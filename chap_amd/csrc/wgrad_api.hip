@@ -36,7 +36,8 @@ static int wg_make_plan(const chap_wgrad_params* p, wg_plan* q) {
         const char* e = getenv("CHAP_WGRAD_WP");        // (read per call: the tests force the kernel onto small ragged grids)
         const long wp_min = e ? atol(e) : 1;
         const long t8 = (long)p->N * cdiv(p->H, 8) * cdiv(p->W, 16);
-        if (p->dims == 2 && p->ksize == 3 && p->stride == 1 && p->combine == 0 && p->dtype == CHAP_BF16 && wp_min > 0 && t8 >= wp_min &&
+        // (D == 1: the kernel walks N images of H x W; dims = 2 with D > 1 -- N*D slices -- takes the slab kernel)
+        if (p->dims == 2 && p->D == 1 && p->ksize == 3 && p->stride == 1 && p->combine == 0 && p->dtype == CHAP_BF16 && wp_min > 0 && t8 >= wp_min &&
             p->a[0].C <= 256 && p->a[0].C % 16 == 0 && (p->na < 2 || (p->a[1].C <= 256 && p->a[1].C % 16 == 0)) && p->b.C <= 256) { q->brick = 2; q->KC = 16; }
     }
     // (tried: 16 x 16 tiles for the 2D 16-channel levels -- 16->16 at 256x256 35.8 -> 32.9 us with 512 blocks, 16+16->16 unchanged: not kept)

@@ -31,6 +31,14 @@ def test_wgrad_conv3x3(dtype, cin, cout, hw):
     tol = 1e-4 if dtype == torch.float32 else 2e-2
     assert relerr(dw - 0.5, w.grad) < tol
     assert relerr(db, gy.sum((0, 2, 3))) < tol
+    # per element against fp64, with the bound of tests/kernel_ref.py
+    from tests import kernel_ref as kr
+    av, flip = kr.operand(x, dtype, scale=sc, shift=sh, act=True, slope=0.01)
+    rw = kr.wgrad_ref(av, gy.double(), ksize=3, stride=1, flipA=flip)
+    prior = torch.full((9, cin, cout), 0.5, dtype=torch.float64)
+    st = (1, 9, cin * 9)
+    kr.check("dW", dw, kr.to_layout(rw["dw"] + prior, st, dw.shape), kr.to_layout(kr.wgrad_bound(rw, prior), st, dw.shape))
+    kr.check("db", db, rw["db"], kr.wgrad_bound(rw, which="db"))
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
@@ -48,6 +56,9 @@ def test_wgrad_concat_1x1_deconv_down(dtype):
     ops.wgrad([ops.Lazy(cl(x0, dtype)), ops.Lazy(cl(x1, dtype))], ops.Lazy(cl(gy, dtype)), dw, (1, 9, 32 * 9),
               grid=(N, 1, H, W), in_dims=(1, H, W), ksize=3, stride=1, dims=2)
     assert relerr(dw, w.grad) < tol
+    from tests import kernel_ref as kr
+    rw = kr.wgrad_ref(torch.cat((x0, x1), 1).double(), gy.double(), ksize=3, stride=1)
+    kr.check("dW concat", dw, kr.to_layout(rw["dw"], (1, 9, 32 * 9), dw.shape), kr.to_layout(kr.wgrad_bound(rw), (1, 9, 32 * 9), dw.shape))
     # 1x1 conv 64 -> 32
     x = rq(torch.randn(N, 64, H, W, generator=g), dtype)
     gy = rq(torch.randn(N, 32, H, W, generator=g), dtype)
@@ -56,6 +67,8 @@ def test_wgrad_concat_1x1_deconv_down(dtype):
     dw = torch.zeros(32, 64, 1, 1, device=DEV)
     ops.wgrad([ops.Lazy(cl(x, dtype))], ops.Lazy(cl(gy, dtype)), dw, (1, 1, 64), grid=(N, 1, H, W), in_dims=(1, H, W), ksize=1, stride=1, dims=2)
     assert relerr(dw, w.grad) < tol
+    rw = kr.wgrad_ref(x.double(), gy.double(), ksize=1, stride=1)
+    kr.check("dW 1x1", dw, kr.to_layout(rw["dw"], (1, 1, 64), dw.shape), kr.to_layout(kr.wgrad_bound(rw), (1, 1, 64), dw.shape))
     # transposed conv k2 s2 2D: dW[ci][co][sub] = sum_p x[p][ci] * g[2p+sub][co]  (roles swapped)
     x = rq(torch.randn(N, 64, H, W, generator=g), dtype)
     gy = rq(torch.randn(N, 32, 2 * H, 2 * W, generator=g), dtype)
@@ -66,6 +79,8 @@ def test_wgrad_concat_1x1_deconv_down(dtype):
     # kernel: A = fine gradient (kc = co), B = coarse input (kn = ci): strides (tap, kc=co, kn=ci)
     ops.wgrad([ops.Lazy(cl(gy, dtype))], ops.Lazy(cl(x, dtype)), dw, (1, 4, 32 * 4), grid=(N, 1, H, W), in_dims=(1, 2 * H, 2 * W), ksize=2, stride=2, dims=2)
     assert relerr(dw, w.grad) < tol
+    rw = kr.wgrad_ref(gy.double(), x.double(), ksize=2, stride=2)
+    kr.check("dW deconv", dw, kr.to_layout(rw["dw"], (1, 4, 32 * 4), dw.shape), kr.to_layout(kr.wgrad_bound(rw), (1, 4, 32 * 4), dw.shape))
     # 3D down conv k2 s2 16 -> 32
     x = rq(torch.randn(1, 16, 8, 8, 16, generator=g), dtype)
     gy = rq(torch.randn(1, 32, 4, 4, 8, generator=g), dtype)
@@ -74,6 +89,8 @@ def test_wgrad_concat_1x1_deconv_down(dtype):
     dw = torch.zeros(32, 16, 2, 2, 2, device=DEV)
     ops.wgrad([ops.Lazy(cl(x, dtype))], ops.Lazy(cl(gy, dtype)), dw, (1, 8, 16 * 8), grid=(1, 4, 4, 8), in_dims=(8, 8, 16), ksize=2, stride=2, dims=3)
     assert relerr(dw, w.grad) < tol
+    rw = kr.wgrad_ref(x.double(), gy.double(), ksize=2, stride=2)
+    kr.check("dW 3D down", dw, kr.to_layout(rw["dw"], (1, 8, 16 * 8), dw.shape), kr.to_layout(kr.wgrad_bound(rw), (1, 8, 16 * 8), dw.shape))
     # 3D 3^3 conv 32 -> 16
     x = rq(torch.randn(1, 32, 5, 9, 16, generator=g), dtype)
     gy = rq(torch.randn(1, 16, 5, 9, 16, generator=g), dtype)
@@ -82,6 +99,8 @@ def test_wgrad_concat_1x1_deconv_down(dtype):
     dw = torch.zeros(16, 32, 3, 3, 3, device=DEV)
     ops.wgrad([ops.Lazy(cl(x, dtype))], ops.Lazy(cl(gy, dtype)), dw, (1, 27, 32 * 27), grid=(1, 5, 9, 16), in_dims=(5, 9, 16), ksize=3, stride=1, dims=3)
     assert relerr(dw, w.grad) < tol
+    rw = kr.wgrad_ref(x.double(), gy.double(), ksize=3, stride=1)
+    kr.check("dW 3D 3^3", dw, kr.to_layout(rw["dw"], (1, 27, 32 * 27), dw.shape), kr.to_layout(kr.wgrad_bound(rw), (1, 27, 32 * 27), dw.shape))
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
@@ -117,6 +136,12 @@ def test_act_bn_backward_with_pool(dtype):
     tol = 2e-4 if dtype == torch.float32 else 3e-2
     assert relerr(uncl(gout).squeeze(2), r.grad) < tol
     assert relerr(dgamma, gm.grad) < tol and relerr(dbeta, bt.grad) < tol
+    from tests import kernel_ref as kr
+    ref = kr.act_bwd_ref(raw, [ga, rq(gb, dtype)], scale=scale, shift=shift, act=True, slope=0.01, keep=keep, keep_scale=1 / 0.8, g_pool=gp,
+                         pool_idx=uncl(idx).squeeze(2), bn_mode=1, mean=mean, invstd=invstd, gamma_=gamma, count=cnt)
+    kr.check("gout", uncl(gout).squeeze(2), ref["g"], kr.bound(ref["g"], extra=ref["g_bound"], store=dtype))
+    kr.check("dgamma", dgamma, ref["S1"], kr.param_grad_bound(ref["S1"], ref["b1"]))
+    kr.check("dbeta", dbeta, ref["S0"], kr.param_grad_bound(ref["S0"], ref["b0"]))
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
@@ -138,6 +163,14 @@ def test_first_conv_backward(dtype, dims):
     tol = 1e-4 if dtype == torch.float32 else 1e-2
     assert relerr(dx, xin.grad.reshape(shape)) < tol
     assert relerr(dw, w.grad) < tol and relerr(db, b.grad) < tol
+    from tests import kernel_ref as kr
+    gyd = gy.double()
+    rw = kr.wgrad_ref(xin.detach().double(), gyd, ksize=3, stride=1)
+    taps = 3 ** dims
+    kr.check("c1 dW", dw, kr.to_layout(rw["dw"], (1, taps, taps), w.shape), kr.to_layout(kr.wgrad_bound(rw), (1, taps, taps), w.shape))
+    kr.check("c1 db", db, rw["db"], kr.wgrad_bound(rw, which="db"))
+    r = kr.conv_ref(kr.PACK_CONV_DGRAD, gyd, w.detach().double())
+    kr.check("c1 dx", dx.reshape(r["y"].shape), r["y"], kr.conv_bound(r, torch.float32))
 
 
 def test_losses_vs_oracle():
@@ -340,6 +373,14 @@ def test_wgrad_conv3d_ragged(dtype, shape, cin, cout, add2, brick, monkeypatch):
     tol = 1e-4 if dtype == torch.float32 else 2e-2
     assert relerr(dw - 0.25, w.grad) < tol
     assert relerr(db, gy.sum((0, 2, 3, 4))) < tol
+    from tests import kernel_ref as kr
+    parts = [kr.lazy_f32(x, scale=sc, shift=sh, act=True, slope=0.0, chan_mul=cm)] + ([kr.lazy_f32(x1)] if add2 else [])
+    av, flip = kr.mfma_operand(*(kr.add_f32(parts) if add2 else parts[0]), dtype)
+    rw = kr.wgrad_ref(av, gy.double(), ksize=3, stride=1, flipA=flip)
+    prior = torch.full((27, cin, cout), 0.25, dtype=torch.float64)
+    st = (1, 27, cin * 27)
+    kr.check("dW", dw, kr.to_layout(rw["dw"] + prior, st, dw.shape), kr.to_layout(kr.wgrad_bound(rw, prior), st, dw.shape))
+    kr.check("db", db, rw["db"], kr.wgrad_bound(rw, which="db"))
 
 
 @pytest.mark.parametrize("mr", [2, 1])
@@ -383,4 +424,145 @@ def test_wgrad_wave_private_2d(cins, cout, hw, keep, mr, monkeypatch):
         outs[wp] = (dw.cpu() - 0.5, db.cpu())
     assert relerr(outs["1"][0], w.grad) < 2e-2 and relerr(outs["1"][1], gy[:, :cout].sum((0, 2, 3))) < 2e-2
     assert relerr(outs["1"][0], outs["0"][0]) < 2e-5 and relerr(outs["1"][1], outs["0"][1]) < 2e-5      # same products, another summation order
+    from tests import kernel_ref as kr
+    vs = [kr.lazy_f32(x, scale=sc, shift=sh, act=True, slope=0.01, keep=km if (i == 0 and keep) else None, keep_scale=1.25 if (i == 0 and keep) else 1.0)
+          for i, (x, (sc, sh)) in enumerate(zip(xs, aff))]
+    av, flip = kr.mfma_operand(torch.cat([v[0] for v in vs], 1), torch.cat([v[1] for v in vs], 1), dtype)
+    rw = kr.wgrad_ref(av, gy[:, :cout].double(), ksize=3, stride=1, flipA=flip)
+    st = (1, 9, cin * 9)
+    for wp in ("1", "0"):
+        kr.check("dW[wp=%s]" % wp, outs[wp][0], kr.to_layout(rw["dw"], st, (cout, cin, 3, 3)), kr.to_layout(kr.wgrad_bound(rw, torch.full((9, cin, cout), 0.5)), st, (cout, cin, 3, 3)))
+        kr.check("db[wp=%s]" % wp, outs[wp][1], rw["db"], kr.wgrad_bound(rw, which="db"))
     assert float(outs["1"][0].abs().max()) > 0
+
+
+def _act_matrix_case(case, C):
+    """(shape N, D, H, W; incoming gradients; pooled gradient; bn mode; keep mask; channel multipliers)"""
+    ppb = 256 // (C // 8)                                  # pixels per block step
+    if case == "2d_small":                                 # a handful of blocks
+        return (2, 1, 6, 10), 2, True, 1, True, False
+    if case == "2d_capped":                                # > 2 x 512 blocks' worth of pixels: every thread of the 512 capped blocks loops
+        W = 72
+        return (2, 1, 2 * -(-(1100 * ppb) // (4 * W)), W), 0, True, 1, False, False
+    if case == "3d_bn2":                                   # fixed affine, dgamma / dbeta from the same reduction, Dropout3d multipliers
+        return (2, 3, 5, 12), 3, False, 2, False, True
+    return (1, 4, 6, 7), 1, False, 0, False, True          # "3d_bn0"
+
+
+@pytest.mark.parametrize("case", ["2d_small", "2d_capped", "3d_bn2", "3d_bn0"])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("C", [8, 16, 32, 64, 128, 256])
+def test_act_bwd_matrix(C, dtype, case):
+    """chap_act_bwd_reduce / _apply over the channel counts it accepts (C8 = 1 .. 32: each has its own lane pattern in the partial
+    reduction), 2D with a pooled gradient and 3D with channel multipliers, a few blocks and the 512-block cap with its grid-stride loop,
+    bn modes 0 / 1 / 2, 0..3 same-grid gradient sources -- gout, dgamma, dbeta against the fp64 restatement with the per-element bound
+    (tests/kernel_ref.py), and bit for bit on a second launch."""
+    from tests import kernel_ref as kr
+    (N, D, H, W), ng, pool, bn, with_keep, with_cm = _act_matrix_case(case, C)
+    g = torch.Generator().manual_seed(70 + C)
+    sp = (H, W) if D == 1 else (D, H, W)
+    raw = rq(torch.randn(N, C, *sp, generator=g) * 1.5 + 0.3, dtype)
+    gamma, beta = torch.rand(C, generator=g) + 0.5, torch.randn(C, generator=g) * 0.2
+    red = [0] + list(range(2, raw.dim()))
+    mean = raw.double().mean(red).float()
+    invstd = (raw.double().var(red, unbiased=False) + 1e-5).rsqrt().float()
+    scale = gamma * invstd
+    shift = beta - mean * scale
+    keep = (torch.rand(N, C, *sp, generator=g) > 0.2).float() if with_keep else None
+    cm = (torch.rand(N, C, generator=g) > 0.3).float() * 1.5 if with_cm else None
+    grads = [rq(torch.randn(N, C, *sp, generator=g), dtype) for _ in range(ng)]
+    gp = rq(torch.randn(N, C, H // 2, W // 2, generator=g), dtype) if pool else None
+    idx = torch.randint(0, 4, (N, C, H // 2, W // 2), generator=g).to(torch.uint8) if pool else None
+    cnt = raw[:, 0].numel()
+    ref = kr.act_bwd_ref(raw, grads, scale=scale, shift=shift, act=True, slope=0.01, keep=keep, keep_scale=1.25, chan_mul=cm,
+                         g_pool=gp, pool_idx=idx, bn_mode=bn, mean=mean if bn else None, invstd=invstd, gamma_=gamma, count=cnt)
+    lz = ops.Lazy(cl(raw, dtype), scale.to(DEV), shift.to(DEV), True, 0.01, keep=None if keep is None else cl(keep, torch.uint8),
+                  keep_scale=1.25, chan_mul=None if cm is None else cm.to(DEV))
+    glist = []
+    for i, gr in enumerate(grads):                         # the second source sits inside a wider buffer (ld = 2C, coff = C)
+        if i == 1:
+            wide = torch.zeros(*cl(gr, dtype).shape[:4], 2 * C, device=DEV, dtype=dtype)
+            wide[..., C:] = cl(gr, dtype)
+            glist.append((wide, C))
+        else:
+            glist.append((cl(gr, dtype), 0))
+    prior = torch.randn(2, C, generator=g)                 # dgamma / dbeta accumulate (+=)
+
+    def launch():
+        gout = torch.full((N, D, H, W, C), float("nan"), device=DEV, dtype=dtype)
+        dgamma, dbeta = prior[0].to(DEV), prior[1].to(DEV)
+        kw = dict(g_pool=cl(gp, dtype), pool_idx=cl(idx, torch.uint8)) if pool else {}
+        if bn:
+            kw.update(mean=mean.to(DEV), invstd=invstd.to(DEV), gamma=gamma.to(DEV), dgamma=dgamma, dbeta=dbeta, count=cnt, bn_mode=bn)
+        ops.act_bwd(lz, glist, gout, **kw)
+        torch.cuda.synchronize()
+        return gout, dgamma, dbeta
+
+    gout, dgamma, dbeta = launch()
+    got = uncl(gout) if D > 1 else uncl(gout).squeeze(2)
+    w = [kr.check("gout", got, ref["g"], kr.bound(ref["g"], extra=ref["g_bound"], store=dtype))]
+    if bn:
+        w.append(kr.check("dbeta", dbeta, ref["S0"] + prior[1].double(), kr.param_grad_bound(ref["S0"], ref["b0"], prior[1])))
+        w.append(kr.check("dgamma", dgamma, ref["S1"] + prior[0].double(), kr.param_grad_bound(ref["S1"], ref["b1"], prior[0])))
+    print("act_bwd C=%d %s %s: worst err/bound %s" % (C, dtype, case, " ".join("%.3f" % v for v in w)))
+    again = launch()
+    assert torch.equal(again[0].view(torch.uint8), gout.view(torch.uint8))
+    assert torch.equal(again[1], dgamma) and torch.equal(again[2], dbeta)
+
+
+@pytest.mark.parametrize("c", [16, 32])
+@pytest.mark.parametrize("D", [2, 3])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_conv_wgrad_dims2_depth_slices(dtype, D, c, monkeypatch):
+    """dims = 2 with D > 1: a 2D conv and weight gradient over the N*D slices (include/chap_hip.h, `dims`) -- lazy BatchNorm-affine +
+    LeakyReLU source, bias, shifted statistics, bias gradient, accumulation into existing dW -- against the fp64 restatement with the
+    per-element bound, with the default dispatch and with CHAP_CONV_WP=0 / CHAP_WGRAD_WP=0.  (The wave-private kernels walk N images of
+    H x W only; the dispatch keeps these launches off them -- both settings must reach the same generic kernels, so the two results
+    are also compared bit for bit.  Before that guard, the default dispatch left the slices n >= N unwritten.)"""
+    from tests import kernel_ref as kr
+    g = torch.Generator().manual_seed(81)
+    N, H, W = 2, 20, 24
+    x = rq(torch.randn(N * D, c, H, W, generator=g), dtype)
+    sc, sh = torch.rand(c, generator=g) + 0.5, torch.randn(c, generator=g) * 0.2
+    w = torch.randn(c, c, 3, 3, generator=g) / (c * 9) ** 0.5
+    b = torch.randn(c, generator=g) * 0.1
+    gy = rq(torch.randn(N * D, c, H, W, generator=g), dtype)
+    cs = torch.randn(c, generator=g)
+    a, flip = kr.operand(x, dtype, scale=sc, shift=sh, act=True, slope=0.01)
+    r = kr.conv_ref(kr.PACK_CONV_FWD, a, kr.weight_operand(w, dtype), b, flip=flip)
+    (s1, b1), (s2, b2) = kr.stats_ref(r, cs)
+    rw = kr.wgrad_ref(a, gy.double(), ksize=3, stride=1, flipA=flip)
+    st = (1, 9, c * 9)
+    prior = torch.full((9, c, c), 0.5, dtype=torch.float64)
+    dw_ref, dw_bnd = kr.to_layout(rw["dw"] + prior, st, w.shape), kr.to_layout(kr.wgrad_bound(rw, prior), st, w.shape)
+
+    def dev(t):                                            # [N*D, C, H, W] -> [N, D, H, W, C]
+        return t.view(N, D, c, H, W).permute(0, 1, 3, 4, 2).contiguous().to(DEV, dtype)
+
+    lz = ops.Lazy(dev(x), sc.to(DEV), sh.to(DEV), True, 0.01)
+    wp = ops.pack_weights(w.to(DEV), L.PACK_CONV_FWD, dtype, c, c, 9)
+    outs = {}
+    for knob in ("default", "0"):
+        for k in ("CHAP_CONV_WP", "CHAP_WGRAD_WP"):
+            if knob == "default":
+                monkeypatch.delenv(k, raising=False)
+            else:
+                monkeypatch.setenv(k, knob)
+        out = torch.full((N, D, H, W, c), float("nan"), device=DEV, dtype=dtype)
+        stats = ops.stats_buffer(c, DEV)
+        ops.conv_fwd([lz], wp, b.to(DEV), c, out, grid=(N, D, H, W), in_dims=(D, H, W), ksize=3, stride=1, dims=2, stats=stats,
+                     stats_shift=cs.to(DEV))
+        dw = torch.full((c, c, 3, 3), 0.5, device=DEV)
+        db = torch.zeros(c, device=DEV)
+        ops.wgrad([lz], ops.Lazy(dev(gy)), dw, st, grid=(N, D, H, W), in_dims=(D, H, W), ksize=3, stride=1, dims=2, db=db)
+        torch.cuda.synchronize()
+        o = out.float().cpu().permute(0, 1, 4, 2, 3).reshape(N * D, c, H, W)
+        s = ops.stats_totals(stats, c).cpu()
+        kr.check("out[%s]" % knob, o, r["y"], kr.conv_bound(r, dtype))
+        kr.check("stats S[%s]" % knob, s[0], s1, b1)
+        kr.check("stats Q[%s]" % knob, s[1], s2, b2)
+        kr.check("dW[%s]" % knob, dw, dw_ref, dw_bnd)
+        kr.check("db[%s]" % knob, db, rw["db"], kr.wgrad_bound(rw, which="db"))
+        outs[knob] = (out.cpu(), dw.cpu(), db.cpu())
+    assert torch.equal(outs["default"][0].view(torch.uint8), outs["0"][0].view(torch.uint8))
+    assert relerr(outs["default"][1] - 0.5, outs["0"][1] - 0.5) < 2e-5 and relerr(outs["default"][2], outs["0"][2]) < 2e-5

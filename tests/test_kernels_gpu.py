@@ -8,6 +8,7 @@ pytestmark = pytest.mark.gpu
 
 from chap_amd import _lib as L
 from chap_amd import ops
+from tests import kernel_ref as kr
 
 DEV = "cuda"
 TOL = {torch.float32: 2e-5, torch.bfloat16: 2.5e-2}
@@ -67,6 +68,11 @@ def test_conv3x3_2d_plain(dtype, cin, cout, hw):
     rc = ref - c0.view(1, -1, 1, 1)
     assert relerr(s[0], rc.sum((0, 2, 3))) < 1e-3 + TOL[dtype]
     assert relerr(s[1], (rc * rc).sum((0, 2, 3))) < 1e-3 + TOL[dtype]
+    r = kr.conv_ref(kr.PACK_CONV_FWD, x.double(), kr.weight_operand(w, dtype), b)
+    kr.check("out", uncl(out).squeeze(2), r["y"], kr.conv_bound(r, dtype))
+    (s1, b1), (s2, b2) = kr.stats_ref(r, c0)
+    kr.check("stats S", ops.stats_totals(stats, cout)[0], s1, b1)
+    kr.check("stats Q", ops.stats_totals(stats, cout)[1], s2, b2)
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
@@ -90,6 +96,11 @@ def test_conv3x3_concat_lazy_sources(dtype):
     ops.conv_fwd([s0, s1], wp, None, cout, out, grid=(N, 1, H, W), in_dims=(1, H, W), ksize=3, stride=1, dims=2)
     torch.cuda.synchronize()
     assert relerr(uncl(out).squeeze(2), ref) < TOL[dtype]
+    v0 = kr.lazy_f32(x0, scale=sc0, shift=sh0, act=True, slope=0.01, keep=keep, keep_scale=1 / 0.7)
+    v1 = kr.lazy_f32(x1, scale=sc1, shift=sh1, act=True, slope=0.01)
+    av, flip = kr.mfma_operand(torch.cat((v0[0], v1[0]), 1), torch.cat((v0[1], v1[1]), 1), dtype)
+    r = kr.conv_ref(kr.PACK_CONV_FWD, av, kr.weight_operand(w, dtype), flip=flip)
+    kr.check("out", uncl(out).squeeze(2), r["y"], kr.conv_bound(r, dtype))
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
@@ -104,6 +115,8 @@ def test_conv1x1_and_planar_head(dtype):
     out = torch.empty(N, 1, H, W, 32, device=DEV, dtype=dtype)
     ops.conv_fwd([ops.Lazy(cl(x, dtype))], wp, b.to(DEV), 32, out, grid=(N, 1, H, W), in_dims=(1, H, W), ksize=1, stride=1, dims=2)
     assert relerr(uncl(out).squeeze(2), ref) < TOL[dtype]
+    r = kr.conv_ref(kr.PACK_CONV_FWD, x.double(), kr.weight_operand(w, dtype), b)
+    kr.check("1x1 out", uncl(out).squeeze(2), r["y"], kr.conv_bound(r, dtype))
     # 3x3 head 16 -> 4, fp32 planar (NCHW) logits
     x = rq(torch.randn(N, 16, H, W, generator=g), dtype)
     w = torch.randn(4, 16, 3, 3, generator=g) / 12
@@ -114,6 +127,8 @@ def test_conv1x1_and_planar_head(dtype):
     ops.conv_fwd([ops.Lazy(cl(x, dtype))], wp, b.to(DEV), 4, out, grid=(N, 1, H, W), in_dims=(1, H, W), ksize=3, stride=1, dims=2,
                  out_planar=True, out_f32=True)
     assert relerr(out, ref) < TOL[dtype]
+    r = kr.conv_ref(kr.PACK_CONV_FWD, x.double(), kr.weight_operand(w, dtype), b)
+    kr.check("planar head", out, r["y"], kr.conv_bound(r, torch.float32))
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
@@ -131,6 +146,8 @@ def test_deconv_k2s2_2d_and_dgrads(dtype):
                  out_mode=1, out_cn=cout, out_coff=cout)
     assert relerr(uncl(out[..., cout:]).squeeze(2), ref) < TOL[dtype]
     assert out[..., :cout].abs().max().item() == 0
+    r = kr.conv_ref(kr.PACK_DECONV_FWD, x.double(), kr.weight_operand(w, dtype), b)
+    kr.check("deconv out", uncl(out[..., cout:]).squeeze(2), r["y"], kr.conv_bound(r, dtype))
     # deconv input-gradient: d_in = conv k2 s2 of the output gradient
     gy = rq(torch.randn(N, cout, 2 * H, 2 * W, generator=g), dtype)
     ref_dx = F.conv2d(gy, rq(w, dtype), None, stride=2)
@@ -138,6 +155,8 @@ def test_deconv_k2s2_2d_and_dgrads(dtype):
     dx = torch.empty(N, 1, H, W, cin, device=DEV, dtype=dtype)
     ops.conv_fwd([ops.Lazy(cl(gy, dtype))], wpd, None, cin, dx, grid=(N, 1, H, W), in_dims=(1, 2 * H, 2 * W), ksize=2, stride=2, dims=2)
     assert relerr(uncl(dx).squeeze(2), ref_dx) < TOL[dtype]
+    r = kr.conv_ref(kr.PACK_DECONV_DGRAD, gy.double(), kr.weight_operand(w, dtype))
+    kr.check("deconv dgrad", uncl(dx).squeeze(2), r["y"], kr.conv_bound(r, dtype))
     # conv3x3 input-gradient via flipped/transposed packing
     wc = torch.randn(cout, cin, 3, 3, generator=g) / 24
     gy = rq(torch.randn(N, cout, H, W, generator=g), dtype)
@@ -146,6 +165,8 @@ def test_deconv_k2s2_2d_and_dgrads(dtype):
     dx = torch.empty(N, 1, H, W, cin, device=DEV, dtype=dtype)
     ops.conv_fwd([ops.Lazy(cl(gy, dtype))], wpd, None, cin, dx, grid=(N, 1, H, W), in_dims=(1, H, W), ksize=3, stride=1, dims=2)
     assert relerr(uncl(dx).squeeze(2), ref_dx) < TOL[dtype]
+    r = kr.conv_ref(kr.PACK_CONV_DGRAD, gy.double(), kr.weight_operand(wc, dtype))
+    kr.check("conv dgrad", uncl(dx).squeeze(2), r["y"], kr.conv_bound(r, dtype))
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
@@ -166,6 +187,9 @@ def test_conv3d_family(dtype):
     s0 = ops.Lazy(cl(x0, dtype), sc.to(DEV), sh.to(DEV), True, 0.0, chan_mul=cm.to(DEV))
     ops.conv_fwd([s0, ops.Lazy(cl(x1, dtype))], wp, None, 16, out, grid=(N, D, H, W), in_dims=(D, H, W), ksize=3, stride=1, dims=3, combine=1)
     assert relerr(uncl(out), ref) < 2 * TOL[dtype]
+    av, flip = kr.mfma_operand(*kr.add_f32([kr.lazy_f32(x0, scale=sc, shift=sh, act=True, slope=0.0, chan_mul=cm), kr.lazy_f32(x1)]), dtype)
+    r = kr.conv_ref(kr.PACK_CONV_FWD, av, kr.weight_operand(w, dtype), flip=flip)
+    kr.check("3D add-combine", uncl(out), r["y"], kr.conv_bound(r, dtype))
     # k2 s2 down conv 16 -> 32
     x = rq(torch.randn(N, 16, D, H, W, generator=g), dtype)
     w = torch.randn(32, 16, 2, 2, 2, generator=g) / 11
@@ -175,6 +199,8 @@ def test_conv3d_family(dtype):
     out = torch.empty(N, D // 2, H // 2, W // 2, 32, device=DEV, dtype=dtype)
     ops.conv_fwd([ops.Lazy(cl(x, dtype))], wp, b.to(DEV), 32, out, grid=(N, D // 2, H // 2, W // 2), in_dims=(D, H, W), ksize=2, stride=2, dims=3)
     assert relerr(uncl(out), ref) < TOL[dtype]
+    r = kr.conv_ref(kr.PACK_CONV_FWD, x.double(), kr.weight_operand(w, dtype), b)
+    kr.check("3D down", uncl(out), r["y"], kr.conv_bound(r, dtype))
     # its input gradient (1x1 conv + depth-to-space)
     gy = rq(torch.randn(N, 32, D // 2, H // 2, W // 2, generator=g), dtype)
     ref_dx = F.conv_transpose3d(gy, rq(w, dtype), None, stride=2)
@@ -183,6 +209,8 @@ def test_conv3d_family(dtype):
     ops.conv_fwd([ops.Lazy(cl(gy, dtype))], wpd, None, 8 * 16, dx, grid=(N, D // 2, H // 2, W // 2), in_dims=(D // 2, H // 2, W // 2),
                  ksize=1, stride=1, dims=3, out_mode=1, out_cn=16)
     assert relerr(uncl(dx), ref_dx) < TOL[dtype]
+    r = kr.conv_ref(kr.PACK_DOWN_DGRAD, gy.double(), kr.weight_operand(w, dtype))
+    kr.check("3D down dgrad", uncl(dx), r["y"], kr.conv_bound(r, dtype))
     # transposed conv 3D 64 -> 32 with BN statistics per real channel
     x = rq(torch.randn(N, 64, 3, 5, 6, generator=g), dtype)
     w = torch.randn(64, 32, 2, 2, 2, generator=g) / 8
@@ -199,6 +227,11 @@ def test_conv3d_family(dtype):
     rc = ref - c0.view(1, -1, 1, 1, 1)
     assert relerr(st[0], rc.sum((0, 2, 3, 4))) < 1e-3 + TOL[dtype]
     assert relerr(st[1], (rc * rc).sum((0, 2, 3, 4))) < 1e-3 + TOL[dtype]
+    r = kr.conv_ref(kr.PACK_DECONV_FWD, x.double(), kr.weight_operand(w, dtype), b)
+    kr.check("3D deconv", uncl(out), r["y"], kr.conv_bound(r, dtype))
+    (s1, b1), (s2, b2) = kr.stats_ref(r, c0)
+    kr.check("3D deconv stats S", st[0], s1, b1)
+    kr.check("3D deconv stats Q", st[1], s2, b2)
     # ... and chap_bn_finalize folds the 8 sub-lattice rows: batch statistics of the 32 real channels
     gamma, beta = torch.rand(32, generator=g) + 0.5, torch.randn(32, generator=g)
     scale, shift = torch.empty(32, device=DEV), torch.empty(32, device=DEV)
@@ -217,6 +250,8 @@ def test_conv3d_family(dtype):
     ops.conv_fwd([ops.Lazy(cl(x, dtype))], wp, b.to(DEV), 2, out, grid=(N, D, H, W), in_dims=(D, H, W), ksize=1, stride=1, dims=3,
                  out_planar=True, out_f32=True)
     assert relerr(out, ref) < TOL[dtype]
+    r = kr.conv_ref(kr.PACK_CONV_FWD, x.double(), kr.weight_operand(w, dtype), b)
+    kr.check("3D 1x1x1 head", out, r["y"], kr.conv_bound(r, torch.float32))
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
@@ -244,6 +279,11 @@ def test_first_conv_c1(dtype, dims):
     st = ops.stats_totals(stats, 16).float().cpu()
     assert relerr(st[0], rc.sum(red)) < 1e-3
     assert relerr(st[1], (rc * rc).sum(red)) < 1e-3
+    r = kr.conv_ref(kr.PACK_CONV_FWD, xin.to(dtype).double(), kr.weight_operand(w, dtype), b)      # the image rounded like the weights
+    kr.check("c1 out", got, r["y"], kr.conv_bound(r, dtype))
+    (s1, b1), (s2, b2) = kr.stats_ref(r, c0)
+    kr.check("c1 stats S", ops.stats_totals(stats, 16)[0], s1, b1)
+    kr.check("c1 stats Q", ops.stats_totals(stats, 16)[1], s2, b2)
 
 
 @pytest.mark.parametrize("shape", [(12, 1, 256, 256), (3, 1, 37, 90), (2, 56, 112, 80), (1, 9, 21, 70), (1300, 1, 8, 16)])
@@ -379,6 +419,13 @@ def test_conv3d_bricks_ragged(dtype, shape, c, add2):
     st = ops.stats_totals(stats, c).float().cpu()
     assert relerr(st[0], ref.sum((0, 2, 3, 4))) < 1e-3 + TOL[dtype]
     assert relerr(st[1], (ref * ref).sum((0, 2, 3, 4))) < 1e-3 + TOL[dtype]
+    parts = [kr.lazy_f32(x0, scale=sc, shift=sh, act=True, slope=0.0, chan_mul=cm)] + ([kr.lazy_f32(x1)] if add2 else [])
+    av, flip = kr.mfma_operand(*(kr.add_f32(parts) if add2 else parts[0]), dtype)
+    r = kr.conv_ref(kr.PACK_CONV_FWD, av, kr.weight_operand(w, dtype), b, flip=flip)
+    kr.check("out", uncl(out), r["y"], kr.conv_bound(r, dtype))
+    (s1, b1), (s2, b2) = kr.stats_ref(r)
+    kr.check("stats S", ops.stats_totals(stats, c)[0], s1, b1)
+    kr.check("stats Q", ops.stats_totals(stats, c)[1], s2, b2)
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
@@ -411,6 +458,14 @@ def test_conv3x3_2d_bench_shapes_ragged(dtype, N, hw, cin, cout):
     assert torch.equal(first[:L.STATS_HDR + nslots * 2 * cout].view(torch.int32), stats[:L.STATS_HDR + nslots * 2 * cout].view(torch.int32))
     assert relerr(st[0], ref.sum((0, 2, 3))) < 1e-3 + TOL[dtype]
     assert relerr(st[1], (ref * ref).sum((0, 2, 3))) < 1e-3 + TOL[dtype]
+    # per element against fp64, with the bound of tests/kernel_ref.py
+    from tests import kernel_ref as kr
+    av, flip = kr.operand(x, dtype, scale=sc, shift=sh, act=True, slope=0.01, keep=keep, keep_scale=1.25)
+    r = kr.conv_ref(kr.PACK_CONV_FWD, av, kr.weight_operand(w, dtype), b, flip=flip)
+    kr.check("out", uncl(out).squeeze(2), r["y"], kr.conv_bound(r, dtype))
+    (s1, b1), (s2, b2) = kr.stats_ref(r)
+    kr.check("stats S", st[0], s1, b1)
+    kr.check("stats Q", st[1], s2, b2)
 
 
 @pytest.mark.parametrize("dims,shape,c0,c1,cout", [
@@ -432,6 +487,7 @@ def test_conv3x3_k_parallel(dims, shape, c0, c1, cout, monkeypatch):
     sp = (H, W) if dims == 2 else (D, H, W)
     cin = c0 + c1
     xs, lazies, refs = [], [], []
+    vparts = []
     for ci, c in enumerate([c0, c1]):
         if c == 0:
             continue
@@ -446,6 +502,7 @@ def test_conv3x3_k_parallel(dims, shape, c0, c1, cout, monkeypatch):
         if cm is not None:
             ref = ref * cm.view(N, c, 1, 1, 1)
         refs.append(rq(ref, dtype))
+        vparts.append(kr.lazy_f32(x, scale=sc, shift=sh, act=True, slope=0.01, keep=keep, keep_scale=1.0 / 0.7, chan_mul=cm))
         kd = None if keep is None else cl(keep, torch.uint8)
         lazies.append(ops.Lazy(cl(x, dtype), sc.to(DEV), sh.to(DEV), True, 0.01, keep=kd, keep_scale=1.0 / 0.7,
                                chan_mul=None if cm is None else cm.to(DEV)))
@@ -472,6 +529,13 @@ def test_conv3x3_k_parallel(dims, shape, c0, c1, cout, monkeypatch):
     rc = refc - cshift.view(1, -1, 1, 1, 1)
     assert relerr(s1[0], rc.sum((0, 2, 3, 4))) < 1e-3 + TOL[dtype]
     assert relerr(s1[1], (rc * rc).sum((0, 2, 3, 4))) < 1e-3 + TOL[dtype]
+    av, flip = kr.mfma_operand(torch.cat([p[0] for p in vparts], 1), torch.cat([p[1] for p in vparts], 1), dtype)
+    r = kr.conv_ref(kr.PACK_CONV_FWD, av, kr.weight_operand(w, dtype), b, flip=flip)
+    (t1, b1), (t2, b2) = kr.stats_ref(r, cshift)
+    for mode in ("1", "0"):
+        kr.check("out[kpar=%s]" % mode, got[mode][0] if dims == 3 else got[mode][0].squeeze(2), r["y"], kr.conv_bound(r, dtype))
+        kr.check("stats S[kpar=%s]" % mode, got[mode][1][0], t1, b1)
+        kr.check("stats Q[kpar=%s]" % mode, got[mode][1][1], t2, b2)
 
 
 def test_group_region_contract():
@@ -553,11 +617,13 @@ def test_conv_wave_private_2d(cins, cout, hw, keep, split, monkeypatch):
     N, (H, W) = 3, hw
     cin = sum(cins)
     lazies, refs = [], []
+    vparts = []
     for i, c in enumerate(cins):
         x = rq(torch.randn(N, c, H, W, generator=g), dtype)
         sc, sh = torch.rand(c, generator=g) + 0.5, torch.randn(c, generator=g) * 0.2
         km = (torch.rand(N, c, H, W, generator=g) > 0.3).float() if (keep and i == 0) else None
         refs.append(rq(lazy_ref(x, sc, sh, 0.01, km, 1.25 if km is not None else 1.0), dtype))
+        vparts.append(kr.lazy_f32(x, scale=sc, shift=sh, act=True, slope=0.01, keep=km, keep_scale=1.25 if km is not None else 1.0))
         lazies.append(ops.Lazy(cl(x, dtype), sc.to(DEV), sh.to(DEV), True, 0.01, keep=None if km is None else cl(km, torch.uint8), keep_scale=1.25 if km is not None else 1.0))
     w = torch.randn(cout, cin, 3, 3, generator=g) / (cin * 9) ** 0.5
     b = torch.randn(cout, generator=g)
@@ -584,3 +650,10 @@ def test_conv_wave_private_2d(cins, cout, hw, keep, split, monkeypatch):
     assert relerr(got["1"][1], got["0"][1]) < 1e-4
     rc = ref - cshift.view(1, -1, 1, 1)
     assert relerr(got["1"][1][0], rc.sum((0, 2, 3))) < 1e-3 + TOL[dtype]
+    av, flip = kr.mfma_operand(torch.cat([p[0] for p in vparts], 1), torch.cat([p[1] for p in vparts], 1), dtype)
+    r = kr.conv_ref(kr.PACK_CONV_FWD, av, kr.weight_operand(w, dtype), b, flip=flip)
+    (t1, b1), (t2, b2) = kr.stats_ref(r, cshift)
+    for mode in ("1", "0"):
+        kr.check("out[wp=%s]" % mode, uncl(got[mode][0]).squeeze(2), r["y"], kr.conv_bound(r, dtype))
+        kr.check("stats S[wp=%s]" % mode, got[mode][1][0], t1, b1)
+        kr.check("stats Q[wp=%s]" % mode, got[mode][1][1], t2, b2)
