@@ -203,6 +203,27 @@ class MetricsParams(C.Structure):
 
 METRICS_MAX_AXIS = 4096                        # CHAP_METRICS_MAX_AXIS
 
+AUG_NONE, AUG_ROTFLIP, AUG_ROTATE = range(3)   # CHAP_AUG_*
+
+
+class Augment2dRecord(C.Structure):
+    _fields_ = [("offset", _i64), ("x", _i32), ("y", _i32), ("mode", _i32), ("k", _i32), ("axis", _i32), ("reserved", _i32),
+                ("zoom", C.c_double * 2), ("m", C.c_double * 4), ("off", C.c_double * 2)]
+
+
+class Augment2dParams(C.Structure):
+    _fields_ = [("images", _vp), ("labels", _vp), ("store_elems", _i64), ("records", _vp), ("image_out", _vp), ("label_out", _vp),
+                ("label_i64", _i32), ("B", _i32), ("H", _i32), ("W", _i32)]
+
+
+class Augment3dRecord(C.Structure):
+    _fields_ = [("offset", _i64), ("shape", _i32 * 3), ("corner", _i32 * 3), ("k", _i32), ("axis", _i32)]
+
+
+class Augment3dParams(C.Structure):
+    _fields_ = [("images", _vp), ("labels", _vp), ("store_elems", _i64), ("records", _vp), ("image_out", _vp), ("label_out", _vp),
+                ("label_i64", _i32), ("B", _i32), ("P0", _i32), ("P1", _i32), ("P2", _i32)]
+
 
 class GradSimParams(C.Structure):
     _fields_ = [("gl", _vp), ("gu", _vp), ("score", _vp), ("C", _i32), ("K", _i32), ("ema", _f32)]
@@ -227,6 +248,7 @@ _SIGS = {  # name -> (restype, params struct or None)
     "chap_diff_mask": DiffMaskParams, "chap_sgd_step": SgdParams,
     "chap_sample_channel_sum": SampleChanSumParams, "chap_channel_drop": ChannelDropParams,
     "chap_fold_perturbed": FoldParams, "chap_grad_sim": GradSimParams, "chap_metrics": MetricsParams,
+    "chap_augment2d": Augment2dParams, "chap_augment3d": Augment3dParams,
 }
 _SIZE_FNS = {"chap_pack_size": PackParams, "chap_conv_c1_bwd_ws": ConvC1BwdParams, "chap_wgrad_ws": WgradParams,
              "chap_lcc_ws": LccParams, "chap_metrics_ws": MetricsParams}

@@ -528,3 +528,33 @@ def metrics(a, b, classes, *, ndim, spacing=(1.0, 1.0, 1.0), binary=False, dista
         p.dist, p.ws = dist.data_ptr(), ws.data_ptr()
     L.call("chap_metrics", p, _stream())
     return results, border_a, border_b, dist
+
+
+def augment2d(images, labels, records, image_out, label_out):
+    """chap_augment2d: images fp32 / labels uint8 flat device buffers of one store, records a device uint8 buffer holding
+    B chap_augment2d_record (chap_amd.data fills and uploads them), image_out fp32 [B, 1, H, W], label_out int64 or uint8 [B, H, W];
+    writes both outputs on the current stream."""
+    B, _, H, W = image_out.shape
+    assert images.dtype == torch.float32 and labels.dtype == torch.uint8 and images.numel() == labels.numel()
+    assert image_out.dtype == torch.float32 and image_out.is_contiguous() and label_out.is_contiguous()
+    assert label_out.dtype in (torch.int64, torch.uint8) and tuple(label_out.shape) == (B, H, W)
+    assert records.numel() * records.element_size() >= B * L.C.sizeof(L.Augment2dRecord)
+    p = L.Augment2dParams()
+    p.images, p.labels, p.store_elems, p.records = images.data_ptr(), labels.data_ptr(), images.numel(), records.data_ptr()
+    p.image_out, p.label_out, p.label_i64 = image_out.data_ptr(), label_out.data_ptr(), int(label_out.dtype == torch.int64)
+    p.B, p.H, p.W = B, H, W
+    L.call("chap_augment2d", p, _stream())
+
+
+def augment3d(images, labels, records, image_out, label_out):
+    """chap_augment3d: as augment2d for volumes; image_out fp32 [B, 1, P0, P1, P2], label_out int64 or uint8 [B, P0, P1, P2]."""
+    B, _, P0, P1, P2 = image_out.shape
+    assert images.dtype == torch.float32 and labels.dtype == torch.uint8 and images.numel() == labels.numel()
+    assert image_out.dtype == torch.float32 and image_out.is_contiguous() and label_out.is_contiguous()
+    assert label_out.dtype in (torch.int64, torch.uint8) and tuple(label_out.shape) == (B, P0, P1, P2)
+    assert records.numel() * records.element_size() >= B * L.C.sizeof(L.Augment3dRecord)
+    p = L.Augment3dParams()
+    p.images, p.labels, p.store_elems, p.records = images.data_ptr(), labels.data_ptr(), images.numel(), records.data_ptr()
+    p.image_out, p.label_out, p.label_i64 = image_out.data_ptr(), label_out.data_ptr(), int(label_out.dtype == torch.int64)
+    p.B, p.P0, p.P1, p.P2 = B, P0, P1, P2
+    L.call("chap_augment3d", p, _stream())

@@ -686,6 +686,21 @@ class ChapStep:
             self._staged_evt.record(self._copy_stream)
         self._staged = True
 
+    def stage_from(self, loader):
+        """stage() for a device-resident loader (chap_amd.data.DeviceLoader): instead of a host-to-device copy, the copy stream runs the
+        loader's augmentation kernel straight into the staging buffers -- `loader.next_into(image_out, label_out)` launches on the current
+        stream -- so the batch of iteration n + 1 is built beside iteration n and replay() takes it as it takes any staged batch."""
+        if getattr(self, "_stage_v", None) is None:
+            self._stage_v, self._stage_l = torch.empty_like(self._static_v), torch.empty_like(self._static_l)
+            self._copy_stream = torch.cuda.Stream(device=self._static_v.device)
+            self._staged_evt, self._taken_evt = torch.cuda.Event(), None
+        with torch.cuda.stream(self._copy_stream):
+            if self._taken_evt is not None:
+                self._copy_stream.wait_event(self._taken_evt)      # the previous staged batch has been moved into the static buffers
+            loader.next_into(self._stage_v, self._stage_l)
+            self._staged_evt.record(self._copy_stream)
+        self._staged = True
+
     def replay(self, volume_batch=None, label_batch=None, box_yx=None):
         if volume_batch is None:
             if not getattr(self, "_staged", False):

@@ -3,11 +3,13 @@ signature and outputs (code/train_ours_2D.py:219-463): `args` is the dict of its
 it writes `latest.pth` and `{model}_best_model.pth` (= torch.save(model.state_dict()), :428-435), `val.csv` (:437-449)
 and `log.txt` (:567-570) under `snapshot_path`.
 
-What is NOT here (out of scope): the ACDC h5 readers, RandomGenerator augmentation, TensorBoard /
-wandb.  The data layer is an argument: `args["trainloader"]` / `args["val_volumes"]` may carry any iterable of
-{'image': [B,1,H,W] fp32, 'label': [B,H,W]} dicts / list of (image [1,S,H,W], label [1,S,H,W]) tensors (what the reference's
-valloader yields, :274); without them the
-fixed-seed synthetic generator of chap_amd.synthetic stands in (there is no dataset on the GPU box)."""
+What is NOT here (out of scope): TensorBoard / wandb, the validation-set reader.  The data layer is an
+argument: `args["trainloader"]` / `args["val_volumes"]` may carry any iterable of {'image': [B,1,H,W] fp32, 'label': [B,H,W]}
+dicts / list of (image [1,S,H,W], label [1,S,H,W]) tensors (what the reference's valloader yields, :274).  A loader with
+`next_into` (chap_amd.data.DeviceLoader: slices resident on the device, RandomGenerator as one kernel per batch) feeds the
+captured iteration through ChapStep.stage_from; `args["root_path"]` + `args["labeled_slices"]` (the number of labelled slices at
+the head of `train_slices.list`; the reference's patient -> slice table is not copied) build that loader from the ACDC h5 layout.
+With none of them the fixed-seed synthetic generator of chap_amd.synthetic stands in."""
 import csv
 import logging
 import os
@@ -50,7 +52,14 @@ def train(args, snapshot_path):
     if a.get("dtype", "fp32") == "bf16":
         model.set_compute_dtype(torch.bfloat16)
     step = ChapStep(model, a)
-    loader = a.get("trainloader") or _synthetic_loader(a)
+    loader = a.get("trainloader")
+    if loader is None and a.get("root_path") and a.get("labeled_slices"):
+        from .data import DeviceLoader, SliceStore
+        store = SliceStore.from_h5_dir(a["root_path"], "train", device)
+        n_lab = int(a["labeled_slices"])
+        loader = DeviceLoader(store, range(n_lab), range(n_lab, len(store)), a["batch_size"], a["labeled_bs"], a["image_size"], a["seed"])
+    loader = loader or _synthetic_loader(a)
+    device_fed = a["use_graph"] and hasattr(loader, "next_into")      # the next batch is built on the device, beside the running iteration
     val = a.get("val_volumes")
     if val is None:
         vi, vl = synthetic_batch(a["seed"] + 4242, 8, 0, *a["image_size"], a["num_classes"])
@@ -100,6 +109,9 @@ def train(args, snapshot_path):
             model.train()
         if it >= a["max_iterations"]:
             break
+        if device_fed:
+            step.stage_from(loader)
+            continue
         sampled_batch = next(gen)
         if a["use_graph"]:
             step.stage(sampled_batch["image"], sampled_batch["label"])      # travels while the iteration enqueued above runs

@@ -43,6 +43,7 @@
  *      (+-0 / +1 %); measurements in DESIGN.md section 5.  chap_conv_params.out2 / out2_from (a concat layer's input gradient as two dense
  *      tensors).
  *      Additive, no version change: chap_metrics / chap_metrics_ws (segmentation metrics, new structs only).
+ *      Additive, no version change: chap_augment2d / chap_augment3d (device-resident training input, new structs only).
  */
 #ifndef CHAP_HIP_H
 #define CHAP_HIP_H
@@ -424,6 +425,63 @@ typedef struct {
 } chap_metrics_params;
 size_t chap_metrics_ws(const chap_metrics_params* p);
 int    chap_metrics(const chap_metrics_params* p, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Training input on the device (DESIGN.md "Data layer"): what the reference builds on the host in four DataLoader worker
+ * processes, BaseDataSets + RandomGenerator(image_size) (train_ours_2D.py:258-274; train_ablation_2D.py:116-131), as ONE gather
+ * per output pixel from a slice store that lives in device memory.  dataloaders/dataset.py is absent from the reference: the
+ * transform is the public SSL4MIS RandomGenerator (unpinned), every step of which is order-0 resampling:
+ *     mode 1: flip(rot90(., k), axis)   or   mode 2: ndimage.rotate(., angle, order=0, reshape=False)   or   mode 0: nothing;
+ *     then ndimage.zoom(., (H / x', W / y'), order=0)  with (x', y') the shape after the first step;  image -> fp32 [1][H][W],
+ *     label -> integer [H][W].
+ * Output pixel (o0, o1): zoom coordinate c = o * zoom[axis] (fp64; zoom = (n' - 1) / (n_out - 1), divided on the host), outside
+ * unless 0 <= c <= n' - 1, index floor(c + 0.5) in the intermediate image; mode 1 maps that index to the source with integers;
+ * mode 2 takes it through  c_h = off[h] + i0 * m[h][0] + i1 * m[h][1]  (fp64, in that order, multiply and add rounded SEPARATELY as
+ * scipy's compiled loop does), outside unless 0 <= c_h <= n_h - 1 on both axes, index floor(c_h + 0.5).  Outside in either stage
+ * gives 0 for image and label (scipy's mode='constant').  m and off are the fp64 values ndimage.rotate computes in Python
+ * (special.cosdg / sindg, in_center - m @ out_center).  Bit-identical to the scipy calls (tests/test_augment_cpu.py, _gpu.py).
+ * The records are read from DEVICE memory: the same launch (or a captured one) serves new draws once the table is rewritten. */
+enum { CHAP_AUG_NONE = 0, CHAP_AUG_ROTFLIP = 1, CHAP_AUG_ROTATE = 2 };
+typedef struct {
+    int64_t offset;                /* first element of the source slice in `images` / `labels`                        */
+    int32_t x, y;                  /* its shape [x][y]                                                                */
+    int32_t mode;                  /* CHAP_AUG_*                                                                      */
+    int32_t k, axis;               /* mode 1: quarter turns 0..3, flipped axis 0 / 1                                  */
+    int32_t reserved;
+    double  zoom[2];               /* step of the zoom coordinate per output axis                                     */
+    double  m[4];                  /* mode 2: rotation matrix, row-major                                              */
+    double  off[2];                /* mode 2: offset                                                                  */
+} chap_augment2d_record;
+typedef struct {
+    const float* images;           /* the store: slices back to back, fp32                                            */
+    const uint8_t* labels;         /* same offsets, uint8                                                             */
+    int64_t store_elems;           /* elements in the store (the host checks every record against it BEFORE upload)   */
+    const chap_augment2d_record* records;   /* device [B]                                                             */
+    float* image_out;              /* [B][1][H][W] fp32                                                               */
+    void*  label_out;              /* [B][H][W] int64 (label_i64 = 1, what the training step holds) or uint8          */
+    int32_t label_i64;
+    int32_t B, H, W;               /* H, W >= 2                                                                       */
+} chap_augment2d_params;
+int chap_augment2d(const chap_augment2d_params* p, void* stream);
+
+/* 3D (the project's own definition: there is no 3D training script upstream; the usual LA RandomCrop +
+ * RandomRotFlip): crop at `corner`, rot90(k) in the first two axes, flip(axis in {0, 1}); integer index maps only.  With odd k
+ * the crop is [P1][P0][P2] so that the output has the patch shape [P0][P1][P2].  The host guarantees corner + crop <= shape. */
+typedef struct {
+    int64_t offset;                /* first element of the source volume                                              */
+    int32_t shape[3];              /* its shape                                                                       */
+    int32_t corner[3];             /* first voxel of the crop                                                         */
+    int32_t k, axis;
+} chap_augment3d_record;
+typedef struct {
+    const float* images; const uint8_t* labels; int64_t store_elems;
+    const chap_augment3d_record* records;   /* device [B]                                                             */
+    float* image_out;              /* [B][1][P0][P1][P2] fp32                                                         */
+    void*  label_out;              /* [B][P0][P1][P2] int64 or uint8                                                  */
+    int32_t label_i64;
+    int32_t B, P0, P1, P2;
+} chap_augment3d_params;
+int chap_augment3d(const chap_augment3d_params* p, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Channel-level perturbation: FilterDropout.perform_dropout (FilterDropout.py:45-89) as two kernels.
