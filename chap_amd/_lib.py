@@ -186,7 +186,7 @@ class LccParams(C.Structure):
 
 class DiffMaskParams(C.Structure):
     _fields_ = [("p1", _vp), ("p2", _vp), ("knowledge", _vp), ("out", _vp), ("pooled_ws", _vp),
-                ("N", _i32), ("H", _i32), ("W", _i32), ("scale", _i32), ("topk", _f32)]
+                ("N", _i32), ("H", _i32), ("W", _i32), ("scale", _i32), ("k", _i32)]
 
 
 class MetricResult(C.Structure):
@@ -256,7 +256,7 @@ _SIZE_FNS = {"chap_pack_size": PackParams, "chap_conv_c1_bwd_ws": ConvC1BwdParam
 _lib = None
 
 
-ABI_VERSION = 7            # CHAP_ABI_VERSION of include/chap_hip.h this binding mirrors (checked when the library is loaded)
+ABI_VERSION = 9            # CHAP_ABI_VERSION of include/chap_hip.h this binding mirrors (checked when the library is loaded)
 
 
 class ChapError(RuntimeError):

@@ -176,8 +176,7 @@ __global__ __launch_bounds__(1024) void diffmask_select_kernel(const chap_diffma
     const int PH = P.H / P.scale, PW = P.W / P.scale, M = PH * PW;
     const int n = blockIdx.x;
     const float* v = P.pooled_ws + (long)n * M;
-    int k = (int)(P.topk * (float)M);
-    if (k < 1) k = 1;
+    const int k = P.k;
     if (threadIdx.x == 0) { s_prefix = 0; s_rem = k; }
     unsigned* myh = whist[threadIdx.x >> 6];
     for (int shift = 24; shift >= 0; shift -= 8) {
@@ -249,6 +248,7 @@ __global__ void diffmask_write_kernel(const chap_diffmask_params P, const float*
 extern "C" int chap_diff_mask(const chap_diffmask_params* p, void* stream) {
     CHAP_CHECK_ARG(p && p->p1 && p->p2 && p->knowledge && p->out && p->pooled_ws, "chap_diff_mask: null argument");
     CHAP_CHECK_ARG(p->scale > 0 && p->H % p->scale == 0 && p->W % p->scale == 0, "chap_diff_mask: H,W must be multiples of scale");
+    CHAP_CHECK_ARG(p->k >= 1 && (long)p->k <= (long)(p->H / p->scale) * (p->W / p->scale), "chap_diff_mask: k=%d outside [1, (H/scale)*(W/scale)]", p->k);
     const long total = (long)p->N * (p->H / p->scale) * (p->W / p->scale);
     hipLaunchKernelGGL(diffmask_pool_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *p);
     CHAP_LAUNCH_CHECK("chap_diff_mask(pool)");

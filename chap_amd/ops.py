@@ -438,7 +438,8 @@ def largest_cc(labels, num_classes):
 
 
 def diff_mask(p1, p2, knowledge, scale, topk):
-    """[N, H, W] maps (3D volumes are passed as [N, D*H, W]: in-plane scale x scale patches)."""
+    """[N, H, W] maps (3D volumes are passed as [N, D*H, W]: in-plane scale x scale patches).  The count of selected cells is the
+    definition's k = max(int(topk * M), 1), in Python's double arithmetic as oracle.train_step.create_mask_v1 computes it."""
     if knowledge.dim() == 4:
         n, d, h, w = knowledge.shape
         return diff_mask(p1.reshape(n, d * h, w), p2.reshape(n, d * h, w), knowledge.reshape(n, d * h, w), scale, topk).reshape(n, d, h, w)
@@ -447,7 +448,7 @@ def diff_mask(p1, p2, knowledge, scale, topk):
     ws = L.hold_empty(N * (H // scale) * (W // scale) + N, dtype=torch.float32, device=knowledge.device)
     p = L.DiffMaskParams()
     p.p1, p.p2, p.knowledge, p.out, p.pooled_ws = p1.data_ptr(), p2.data_ptr(), knowledge.data_ptr(), out.data_ptr(), ws.data_ptr()
-    p.N, p.H, p.W, p.scale, p.topk = N, H, W, scale, topk
+    p.N, p.H, p.W, p.scale, p.k = N, H, W, scale, max(int(topk * ((H // scale) * (W // scale))), 1)
     L.call("chap_diff_mask", p, _stream())
     return out
 

@@ -44,6 +44,8 @@
  *      tensors).
  *      Additive, no version change: chap_metrics / chap_metrics_ws (segmentation metrics, new structs only).
  *      Additive, no version change: chap_augment2d / chap_augment3d (device-resident training input, new structs only).
+ *   9  (8 was the in-launch BatchNorm finalize, withdrawn before any release) chap_diffmask_params carries the integer count k instead of the float fraction topk: the library computed (int)(topk_f32 * (float)M),
+ *      one more than the definition's max(int(topk * M), 1) in double for e.g. topk = 0.29, M = 100.  The caller computes k.
  */
 #ifndef CHAP_HIP_H
 #define CHAP_HIP_H
@@ -55,7 +57,7 @@
 extern "C" {
 #endif
 
-#define CHAP_ABI_VERSION 7
+#define CHAP_ABI_VERSION 9
 #define CHAP_STATS_MAX_SLOTS 1024  /* per-block partial slots of the BatchNorm statistics (one per persistent conv block) */
 #define CHAP_STATS_HDR 4           /* floats in front of the slots; word 0 = number of slots in use (int32)                */
 #define CHAP_ACT_BWD_SLOTS 1024    /* per-block partial slots of the BN-backward sums                                      */
@@ -355,9 +357,11 @@ size_t chap_lcc_ws(const chap_lcc_params* p);
 int    chap_largest_cc(const chap_lcc_params* p, void* stream);
 
 /* patch.create_maskV1 (ABSENT from the reference; DESIGN.md "P2"): mask = (p1 != p2) OR
- * nearest-upsample(top-k fraction of avg_pool(knowledge, scale)), per sample. out fp32 [N][H][W]. */
+ * nearest-upsample(the k largest cells of avg_pool(knowledge, scale), ties at the k-th value included), per sample. out fp32 [N][H][W].
+ * k: cells selected per sample, 1 <= k <= M = (H/s)*(W/s); the definition's count for a fraction topk is max((int)(topk * M), 1)
+ * evaluated in DOUBLE (a float product rounds e.g. 0.29 * 100 up to 29) -- the caller computes it. */
 typedef struct { const int64_t* p1; const int64_t* p2; const float* knowledge; float* out; float* pooled_ws; /* N*(H/s)*(W/s) + N floats */
-                 int32_t N, H, W, scale; float topk; } chap_diffmask_params;
+                 int32_t N, H, W, scale; int32_t k; } chap_diffmask_params;
 int chap_diff_mask(const chap_diffmask_params* p, void* stream);
 
 /* Fused SGD(momentum, weight decay) over a flat fp32 parameter buffer (train_ours_2D.py:278,383):

@@ -3,7 +3,8 @@
 Tensors are CPU NC(D)HW (channel first), as the tests build them.  A restatement returns the fp64 value of what the kernel computes
 from the operands the kernel multiplies -- the lazy transform rounded where the kernel rounds it, the weights rounded to the MFMA
 operand type -- together with the sums of absolute terms the bound needs.  `bound` turns those into a per-element bound on
-|kernel - reference|; `check` compares and names the worst element.
+|kernel - reference|; `check` compares and names the worst element.  The second half restates the plumbing kernels (losses, VAT / BCP
+helpers, the counter-based RNG, the perturbation mask, SGD, GradSim) in the same way; what is an integer, a mask or a copy is exact.
 
 Constants, fixed before any GPU run and never fitted to observed errors:
   U32 = 2^-24, U_BF16 = 2^-8   unit roundoff (round to nearest) of an fp32 / bf16 value (24 / 8 significant bits).
@@ -18,6 +19,10 @@ Chain lengths (the n of gamma) of the kernels:
                 slot totals are summed in fp64 (stats_totals / bn_finalize): exact here.
   dW, db        a block's pixel loop over its share of the grid, then the slab reduction over the splits: at most the pixel count.
   act_bwd sums  a thread's grid-stride loop, the shuffle / LDS reduction, an fp64 total over the blocks: at most the pixel count.
+  losses        mix_loss / kl / dice-distance accumulators: a thread's grid-stride loop, the wave shuffle, four waves, one partial row per block,
+                the rows summed in fp64 (sum_partial_rows): at most the launch's pixel count N * P (kl: its 2 * C * N * P terms).
+  l2_normalize  the sum of squares of a sample: a thread's loop, the wave / block reduction, an fp64 total over the slices: at most P.
+  grad_sim      accumulated in fp64: no chain term.  perturb, sgd_step, the RNG, boxes, masks: elementwise, no chain.
 """
 import itertools
 import math
@@ -357,3 +362,451 @@ def check(name, got, ref, bnd, dims="ncdhw"):
         raise AssertionError("%s: worst element (%s) = %s: got %.9g ref %.9g bound %.3g ratio %.3g" % (
             name, ",".join(names), idx, float(got[idx]), float(ref[idx]), float(bnd[idx]), worst))
     return worst
+
+
+# ==== plumbing kernels: losses, VAT helpers, RNG, boxes, diff mask, SGD, GradSim =====================================================
+# Elementwise budget of a SHORT fp32 chain (at most eight roundings: an expf / logf / divide counted as one each, the ROCm installed
+# here ships no ulp table for them): EW = 8 U32 on the sum of the chain's |terms|, the figure act_bwd_ref uses.  A value that is a
+# product of several such chains (the loss gradients: softmax factor x coefficient x softmax factor) gets EW per factor.
+EW = 8 * U32
+SEED_DEV_MIX = 0xD1342543DE82EF95                          # aux.hip: seed + *seed_dev * this (mod 2^64)
+
+
+def softmax_ref(logits):
+    """softmax_px (loss.hip) over dim 1 of fp64 logits [N, C, ...]: p_c = expf(z_c - m) / sum, lse = m + logf(sum).
+    Returns dict(p, lse, e_p, e_lse, zm):
+      e_p   = (EW + |z_c - m| U32) p_c   the chain expf, (C - 1) adds, reciprocal, product (<= 8 roundings for C <= 4) plus the rounding
+                                        of the exponent's argument z_c - m, which expf turns into a relative error of the same size
+      e_lse = EW (|m| + 1)              sum in [1, C] carries <= C + 1 roundings, logf's slope 1/sum <= 1 makes them absolute; logf's own
+                                        rounding on log(sum) <= 1.4; the add's on |lse| <= |m| + 1.4
+      zm    = max_c |z_c - m| per pixel."""
+    z = logits
+    m = z.amax(1, keepdim=True)
+    ex = torch.exp(z - m)
+    s = ex.sum(1, keepdim=True)
+    p = ex / s
+    lse = (m + torch.log(s)).squeeze(1)
+    d = (z - m).abs()
+    return dict(p=p, lse=lse, e_p=(EW + d * U32) * p, e_lse=EW * (m.abs().squeeze(1) + 1.0), zm=d.amax(1))
+
+
+def _onehot(t, C, like):
+    """[N, ...] integer labels -> fp64 [N, C, ...] (all zero for a label outside [0, C))."""
+    return torch.stack([(t == c) for c in range(C)], 1).to(like.dtype)
+
+
+def _dice_partials(I, Z, Y, bI, bZ, bY, s):
+    """r = (2 I + s) / (Z + Y + s) with |dr| from the accumulators' bounds."""
+    num, den = 2 * I + s, Z + Y + s
+    r = num / den
+    return num, den, r, 2 * bI / den + r * (bZ + bY) / den
+
+
+def mix_loss_ref(logits, target_a, target_b=None, mask=None, w_a=1.0, w_b=0.5, smooth=1e-10, k_dice=0.0, k_ce=0.0, gscale=1.0,
+                 gscale_dev=None, prior=None):
+    """chap_mix_loss_fwd / _bwd in fp64.  logits [N, C, *sp]; targets, mask [N, *sp] (mask None: ones; target_b None: target_a).
+    Per part k (a: weight mask, b: weight 1 - mask) the accumulators ce = sum mk (lse - z_t), I_c = sum mk p_c t_c, Z_c = sum mk p_c^2,
+    Y_c = sum mk t_c, msum = sum mk over all N * P pixels, then
+      dice_k = w_k / C sum_c [1 - (2 I_c + s) / (Z_c + Y_c + s)],  ce_k = w_k ce / (msum + 1e-16),  loss_k = kd dice_k + kc ce_k
+      dlogits = gs (kc dz + kd p (dp - dot)),  dz_c = sum_k w_k mk / (msum_k + 1e-16) (p_c - t_kc),
+      dp_c = sum_k w_k / C mk (-2 t_kc / den_kc + num_kc 2 p_c / den_kc^2),  dot = sum_c dp_c p_c         (mix_loss_bwd_kernel).
+    Returns dict(acc [2, 2 + 3C] (layout of row 0 of the workspace), acc_b, loss [3], loss_b, dlogits, dlogits_b).  Bounds:
+      accumulators  gamma(N * P) sum |term| + sum (elementwise error of the term) + U32 |total| (the fp64 total stored as fp32)
+      loss          EW on the |terms| of each short chain (a Dice part, a CE part, the k_dice / k_ce combination), plus the accumulators'
+                    bounds through the partial derivatives
+      dlogits       (3 EW + 2 zm U32) * sum of the ABSOLUTE terms of kc dz + kd p (dp - dot) (each term is a product of at most three short
+                    chains -- softmax, coefficient, softmax -- and both differences cancel), plus the accumulators' bounds through the
+                    partial derivatives, plus U32 |prior + g| when accumulating onto `prior`."""
+    z = _c(logits)
+    N, C = z.shape[:2]
+    total = z[:, 0].numel()
+    sm = softmax_ref(z)
+    p, lse = sm["p"], sm["lse"]
+    s, tiny = _fp32_scalar(smooth), _fp32_scalar(1e-16)
+    dflt = k_dice == 0.0 and k_ce == 0.0
+    kd, kc = (0.5, 0.5) if dflt else (_fp32_scalar(k_dice), _fp32_scalar(k_ce))
+    m = torch.ones_like(lse) if mask is None else _c(mask, z)
+    mks = (m, 1.0 - m)
+    ts = [_onehot(target_a.to(z.device), C, z), _onehot((target_a if target_b is None else target_b).to(z.device), C, z)]
+    ws = (_fp32_scalar(w_a), _fp32_scalar(w_b))
+    red = [0] + list(range(2, z.dim()))
+    g = gamma(total)
+    acc, acc_b, parts, parts_b, per = [], [], [], [], []
+    for k in range(2):
+        mk, t = mks[k], ts[k]
+        mk1 = mk.unsqueeze(1)
+        cepx = lse - (t * z).sum(1)
+        ce = (cepx * mk).sum()
+        b_ce = ((sm["e_lse"] + U32 * cepx.abs()) * mk).sum() + g * (cepx.abs() * mk).sum()
+        I, Z, Y = (p * t * mk1).sum(red), (p * p * mk1).sum(red), (t * mk1).sum(red)
+        bI = (sm["e_p"] * t * mk1).sum(red) + g * I
+        bZ = ((2 * p * sm["e_p"] + U32 * p * p) * mk1).sum(red) + g * Z
+        bY = g * Y
+        msum = mk.sum()
+        bM = g * msum
+        row = torch.cat([ce.reshape(1), I, Z, Y, msum.reshape(1)])
+        rb = torch.cat([b_ce.reshape(1), bI, bZ, bY, bM.reshape(1)]) + U32 * row.abs()
+        b_ce, bI, bZ, bY, bM = rb[0], rb[1:1 + C], rb[1 + C:1 + 2 * C], rb[1 + 2 * C:1 + 3 * C], rb[1 + 3 * C]
+        acc.append(row), acc_b.append(rb)
+        num, den, r, dr = _dice_partials(I, Z, Y, bI, bZ, bY, s)
+        w = ws[k]
+        dice = w / C * (1.0 - r).sum()
+        e_dice = EW * w / C * (1.0 + r).sum() + w / C * dr.sum()
+        cek = w * ce / (msum + tiny)
+        e_cek = EW * cek.abs() + w * b_ce / (msum + tiny) + cek.abs() * bM / (msum + tiny)
+        parts.append(kd * dice + kc * cek)
+        parts_b.append(kd * e_dice + kc * e_cek + EW * ((kd * dice).abs() + (kc * cek).abs()))
+        per.append(dict(mk=mk, mk1=mk1, t=t, w=w, num=num, den=den, msum=msum, bI=bI, bZ=bZ, bY=bY, bM=bM))
+    loss = torch.stack([parts[0], parts[1], parts[0] + parts[1]])
+    loss_b = torch.stack([parts_b[0], parts_b[1], parts_b[0] + parts_b[1] + U32 * (parts[0] + parts[1]).abs()])
+    # gradient
+    gs = _fp32_scalar(gscale) * (1.0 if gscale_dev is None else float(gscale_dev))
+    dz, dz_abs, dz_d = torch.zeros_like(p), torch.zeros_like(p), torch.zeros_like(p)
+    dp, dp_abs, dp_d = torch.zeros_like(p), torch.zeros_like(p), torch.zeros_like(p)
+    sh = [1, C] + [1] * (z.dim() - 2)
+    for q in per:
+        kce = q["w"] * q["mk1"] / (q["msum"] + tiny)
+        dz = dz + kce * (p - q["t"])
+        dz_abs = dz_abs + kce * (p + q["t"])
+        dz_d = dz_d + kce / (q["msum"] + tiny) * q["bM"] * (p - q["t"]).abs()
+        num, den = q["num"].reshape(sh), q["den"].reshape(sh)
+        dnum, dden = 2 * q["bI"].reshape(sh), (q["bZ"] + q["bY"]).reshape(sh)
+        co = q["w"] / C * q["mk1"]
+        dp = dp + co * (-2 * q["t"] / den + num * 2 * p / den ** 2)
+        dp_abs = dp_abs + co * (2 * q["t"] / den + num * 2 * p / den ** 2)
+        dp_d = dp_d + co * (2 * q["t"] / den ** 2 * dden + 2 * p / den ** 2 * dnum + 4 * num * p / den ** 3 * dden)
+    dot = (dp * p).sum(1, keepdim=True)
+    gz = gs * (kc * dz + kd * p * (dp - dot))
+    A = abs(gs) * (kc * dz_abs + kd * p * (dp_abs + (dp_abs * p).sum(1, keepdim=True)))
+    prop = abs(gs) * (kc * dz_d + kd * p * (dp_d + (dp_d * p).sum(1, keepdim=True)))
+    gb = (3 * EW + 2 * sm["zm"].unsqueeze(1) * U32) * A + prop
+    if prior is not None:
+        gz = gz + _c(prior, z)
+        gb = gb + U32 * gz.abs()
+    return dict(acc=torch.stack(acc), acc_b=torch.stack(acc_b), loss=loss, loss_b=loss_b, dlogits=gz, dlogits_b=gb, p=p)
+
+
+def pseudo_ref(logits1, logits2):
+    """chap_pseudo_block in fp64: soft1/2 with bound e_p, arg1/2 (first maximum), knowledge = (lse1 - z1[arg2]) + (lse2 - z2[arg1]) with
+    bound e_lse1 + e_lse2 + U32 (|lse1 - z1[arg2]| + |lse2 - z2[arg1]| + |knowledge|), and `near` [N, *sp]: pixels whose two largest
+    probabilities of either head differ, in fp64, by less than those probabilities' bounds (and by more than 0: an exact tie of the
+    logits is an exact tie of the kernel's probabilities, the first index wins there) -- the argmax is undecided there."""
+    out = {}
+    near = None
+    sms = [softmax_ref(_c(l)) for l in (logits1, logits2)]
+    for i, sm in enumerate(sms):
+        top = sm["p"].topk(2, dim=1)
+        gap = top.values[:, 0] - top.values[:, 1]
+        thr = sm["e_p"].gather(1, top.indices).sum(1)
+        nr = (gap > 0) & (gap < thr)
+        near = nr if near is None else near | nr
+        out["soft%d" % (i + 1)], out["soft%d_b" % (i + 1)] = sm["p"], sm["e_p"]
+        out["arg%d" % (i + 1)] = sm["p"].argmax(1)
+    z1, z2 = _c(logits1), _c(logits2)
+    k1 = sms[0]["lse"] - z1.gather(1, out["arg2"].unsqueeze(1)).squeeze(1)
+    k2 = sms[1]["lse"] - z2.gather(1, out["arg1"].unsqueeze(1)).squeeze(1)
+    out["knowledge"] = k1 + k2
+    out["knowledge_b"] = sms[0]["e_lse"] + sms[1]["e_lse"] + U32 * (k1.abs() + k2.abs() + (k1 + k2).abs())
+    out["near"] = near
+    return out
+
+
+NEAR_TIE_CAP = 1e-4                                        # at most 0.01 % of a case's pixels may be left out as near ties
+
+
+def kl_ref(logits, targets, mode="kl", gscale=1.0, gscale_dev=None, prior=0.0):
+    """chap_kl_fwd_bwd in fp64 (two heads; logits / targets: pairs of [N, C, *sp]).  Returns dict(loss, loss_b, g [2], g_b [2]); loss
+    includes the prior value the kernel adds onto.
+      kl    loss += 1/total sum_{h, pixel, c: t > 0} t (log t - (z - lse)),  g_h = gs/total (p - t)
+            term error: EW t (|log t| + |z - lse|) + t e_lse; chain gamma(2 C total); the total times fl(1/total): 3 U32; the += : U32
+            g: EW gs/total (p + t) + gs/total zm U32 p
+      dice  I, Z, Y = sum p t, sum p^2, sum t^2 per head and class; loss += sum_h sum_c (1 - (2I + s)/(Z + Y + s)) / C
+            g_h = gs p (dp - dot), dp_c = (-2 t / den + num 2 p / den^2) / C: bounds as in mix_loss_ref."""
+    gs = _fp32_scalar(gscale) * (1.0 if gscale_dev is None else float(gscale_dev))
+    zs, ts = [_c(l) for l in logits], [_c(t) for t in targets]
+    N, C = zs[0].shape[:2]
+    total = zs[0][:, 0].numel()
+    red = [0] + list(range(2, zs[0].dim()))
+    sh = [1, C] + [1] * (zs[0].dim() - 2)
+    gout, gb = [], []
+    if mode == "kl":
+        val, vb, vabs = 0.0, 0.0, 0.0
+        for z, t in zip(zs, ts):
+            sm = softmax_ref(z)
+            lt = torch.log(t.clamp_min(1e-300))
+            zl = z - sm["lse"].unsqueeze(1)
+            pos = (t > 0).to(z.dtype)
+            term = pos * t * (lt - zl)
+            val = val + term.sum()
+            vabs = vabs + term.abs().sum()
+            vb = vb + (pos * t * (EW * (lt.abs() + zl.abs()) + sm["e_lse"].unsqueeze(1))).sum()
+            gout.append(gs / total * (sm["p"] - t))
+            gb.append(abs(gs) / total * (EW * (sm["p"] + t) + sm["zm"].unsqueeze(1) * U32 * sm["p"]))
+        v = val / total
+        b = (vb + (gamma(2 * C * total) + U32) * vabs) / total + 3 * U32 * abs(v)
+    else:
+        s = _fp32_scalar(1e-10)
+        g = gamma(total)
+        v, b = 0.0, 0.0
+        for z, t in zip(zs, ts):
+            sm = softmax_ref(z)
+            p = sm["p"]
+            I, Z, Y = (p * t).sum(red), (p * p).sum(red), (t * t).sum(red)
+            bI = (sm["e_p"] * t).sum(red) + (g + U32) * (p * t).abs().sum(red) + U32 * I.abs()
+            bZ = (2 * p * sm["e_p"] + U32 * p * p).sum(red) + (g + U32) * Z
+            bY = (g + 2 * U32) * Y
+            num, den, r, dr = _dice_partials(I, Z, Y, bI, bZ, bY, s)
+            v = v + (1.0 - r).sum() / C
+            b = b + (EW * (1.0 + r).sum() + dr.sum()) / C
+            num, den, dnum, dden = num.reshape(sh), den.reshape(sh), 2 * bI.reshape(sh), (bZ + bY).reshape(sh)
+            dp = (-2 * t / den + num * 2 * p / den ** 2) / C
+            dp_abs = (2 * t.abs() / den + num.abs() * 2 * p / den ** 2) / C
+            dp_d = (2 * t.abs() / den ** 2 * dden + 2 * p / den ** 2 * dnum + 4 * num.abs() * p / den ** 3 * dden) / C
+            dot = (dp * p).sum(1, keepdim=True)
+            gout.append(gs * p * (dp - dot))
+            A = abs(gs) * p * (dp_abs + (dp_abs * p).sum(1, keepdim=True))
+            gb.append((3 * EW + 2 * sm["zm"].unsqueeze(1) * U32) * A + abs(gs) * p * (dp_d + (dp_d * p).sum(1, keepdim=True)))
+        b = b + EW * abs(float(v))
+    loss = v + float(prior)
+    return dict(loss=torch.as_tensor(loss, dtype=torch.float64).reshape(1), loss_b=torch.as_tensor(b + U32 * abs(float(loss)), dtype=torch.float64).reshape(1),
+                g=gout, g_b=gb)
+
+
+def l2_normalize_ref(x, eps=1e-8):
+    """chap_l2_normalize: out[n] = x[n] / (sqrt(sum x[n]^2) + eps).  The sum of squares is a P-term fp32 chain (relative gamma(P) on a sum
+    of non-negative terms, halved by the root), then root, add, reciprocal, product: (gamma(P) + EW) |out|.  An all-zero sample: exact 0."""
+    v = _c(x)
+    flat = v.reshape(v.shape[0], -1)
+    nrm = flat.pow(2).sum(1).sqrt().reshape([-1] + [1] * (v.dim() - 1))
+    out = v / (nrm + _fp32_scalar(eps))
+    return out, (gamma(flat.shape[1]) + EW) * out.abs()
+
+
+def perturb_ref(x, d, alpha, mask=None, sign=False):
+    """chap_perturb: out = x + (alpha * mask) * (sign ? sgn(d) : d), sgn(+-0) = 0.  Two products and an add (possibly fused): one rounding
+    per operation on the absolute terms, 3 U32 (|x| + |alpha mask d|)."""
+    xv, dv = _c(x), _c(d)
+    if sign:
+        dv = torch.sign(dv)
+    t = _fp32_scalar(alpha) * (1.0 if mask is None else _c(mask, xv)) * dv
+    return xv + t, 3 * U32 * (xv.abs() + t.abs())
+
+
+def sgd_ref(param, grad, mom, lr, momentum, weight_decay, grad_scale=1.0, grad2=None):
+    """chap_sgd_step: g = grad (+ grad2); gg = g * grad_scale + wd * p; m' = mu * m + gg; p' = p - lr * m'.  Contraction may fuse a product
+    into its add, so each operation is allowed one fp32 rounding on its absolute terms:
+      e_g = U32 |g| (with grad2)   e_gg = gs e_g + 2 U32 (|g gs| + |wd p|)   e_m = e_gg + 2 U32 (|mu m| + |gg|)   e_p = lr e_m + 2 U32 (|p| + |lr m'|)
+    Returns (p', e_p, m', e_m)."""
+    p, g, m = _c(param), _c(grad), _c(mom)
+    lr, mu, wd, gs = (_fp32_scalar(v) for v in (lr, momentum, weight_decay, grad_scale))
+    e_g = torch.zeros_like(g)
+    if grad2 is not None:
+        g = g + _c(grad2, g)
+        e_g = U32 * g.abs()
+    gg = g * gs + wd * p
+    e_gg = abs(gs) * e_g + 2 * U32 * ((g * gs).abs() + (wd * p).abs())
+    m2 = mu * m + gg
+    e_m = e_gg + 2 * U32 * ((mu * m).abs() + gg.abs())
+    p2 = p - lr * m2
+    e_p = abs(lr) * e_m + 2 * U32 * (p.abs() + (lr * m2).abs())
+    return p2, e_p, m2, e_m
+
+
+def grad_sim_ref(gl, gu, score, ema=0.0):
+    """chap_grad_sim: score = ema score + (1 - ema) cos(gl[c], gu[c]) per row; the cosine is accumulated in fp64 and rounded once to fp32,
+    1 - ema once, then two products and an add: 4 U32 (|ema score| + |(1 - ema) sim|).  A zero row: sim = 0 exactly."""
+    a, b = _c(gl).reshape(gl.shape[0], -1), _c(gu).reshape(gu.shape[0], -1)
+    sim = (a * b).sum(1) / (a.pow(2).sum(1).sqrt() * b.pow(2).sum(1).sqrt() + 1e-12)
+    e = _fp32_scalar(ema)
+    t0, t1 = e * _c(score, a), (1.0 - e) * sim
+    return t0 + t1, 4 * U32 * (t0.abs() + t1.abs())
+
+
+# ---- counter-based RNG (aux.hip u01): exact integers ------------------------------------------------------------------------------
+def u01_np(seed, idx, seed_dev=None):
+    """u01(seed, i) of aux.hip in numpy uint64 arithmetic (wraps mod 2^64 as the kernel's does): the 24-bit integer z >> 40; the kernel's
+    float is that integer times 2^-24, exact.  seed_dev: the device word mixed into the seed (None: absent)."""
+    import numpy as np
+    M64 = (1 << 64) - 1
+    sd = (int(seed) + (0 if seed_dev is None else int(seed_dev) * SEED_DEV_MIX)) & M64
+    with np.errstate(over="ignore"):
+        z = np.uint64(sd) + np.uint64(0x9E3779B97F4A7C15) * (np.asarray(idx).astype(np.uint64) + np.uint64(1))
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        z = z ^ (z >> np.uint64(31))
+    return (z >> np.uint64(40)).astype(np.int64)
+
+
+def _s64(v):
+    v &= (1 << 64) - 1
+    return v - (1 << 64) if v >= (1 << 63) else v
+
+
+def _lsr(z, s):
+    return (z >> s) & ((1 << (64 - s)) - 1)
+
+
+def u01_int(seed, n, seed_dev=None, device="cpu"):
+    """u01_np for indices 0..n-1 in torch int64 (two's-complement wrap = the uint64 arithmetic; logical shifts masked), on `device`: the
+    full-size masks of a training step are restated on the GPU.  tests/test_kernel_ref_cpu.py asserts it equals u01_np."""
+    sd = _s64(int(seed) + (0 if seed_dev is None else int(seed_dev) * SEED_DEV_MIX))
+    i = torch.arange(1, n + 1, dtype=torch.int64, device=device)
+    z = i * _s64(0x9E3779B97F4A7C15) + sd
+    z = (z ^ _lsr(z, 30)) * _s64(0xBF58476D1CE4E5B9)
+    z = (z ^ _lsr(z, 27)) * _s64(0x94D049BB133111EB)
+    z = z ^ _lsr(z, 31)
+    return _lsr(z, 40)
+
+
+def keep_mask_ref(seed, n, p, seed_dev=None, device="cpu"):
+    """keep[i] = u01(seed, i) >= p (uint8), the comparison in fp32 as the kernel's: bit-exact."""
+    u = u01_int(seed, n, seed_dev, device).float() * (1.0 / 16777216.0)
+    return (u >= torch.tensor(p, dtype=torch.float32)).to(torch.uint8)
+
+
+def chan_mask_ref(seed, n, p, seed_dev=None, device="cpu"):
+    """mul[i] = u >= p ? 1 / (1 - p) : 0 in fp32 (IEEE divide, subtract): bit-exact."""
+    pf = torch.tensor(p, dtype=torch.float32, device=device)
+    keep = u01_int(seed, n, seed_dev, device).float() * (1.0 / 16777216.0) >= pf
+    return torch.where(keep, 1.0 / (1.0 - pf), torch.zeros((), device=device))
+
+
+def rand_uniform_ref(seed, n, lo, hi, seed_dev=None, device="cpu"):
+    """lo + fl(hi - lo) * u in fp64, and the bound: the multiply-add may be fused or not; unfused, the product's rounding is U32 |d u| even
+    where the sum cancels, so "one fp32 ulp" is taken at the larger of the operands and the result: 2^-23 max(|lo|, |d u|, |value|)."""
+    lo32, hi32 = torch.tensor(lo, dtype=torch.float32), torch.tensor(hi, dtype=torch.float32)
+    d = float(hi32 - lo32)
+    du = d * (u01_int(seed, n, seed_dev, device).double() / 16777216.0)
+    v = float(lo32) + du
+    return v, 2.0 ** -23 * torch.maximum(torch.maximum(du.abs(), v.abs()), torch.full_like(v, abs(float(lo32))))
+
+
+# ---- BCP boxes ------------------------------------------------------------------------------------------------------------------
+def box_inside(shape, box):
+    """bool [*shape] (shape = (H, W) with box (y0, x0, bh, bw), or (D, H, W) with (z0, y0, x0, bd, bh, bw)): inside the box."""
+    nd = len(shape)
+    ins = torch.zeros(shape, dtype=torch.bool)
+    ins[tuple(slice(max(int(box[i]), 0), max(int(box[i]) + int(box[nd + i]), 0)) for i in range(nd))] = True
+    return ins
+
+
+def box_mix_ref(a, b, box):
+    """out = inside ? b : a; a, b [N, (1,) *shape]."""
+    shape = a.shape[-(len(box) // 2):]
+    return torch.where(box_inside(shape, box).to(a.device), b, a)
+
+
+def box_mask_ref(n, shape, box):
+    """int64 [N, *shape]: 0 inside the box, 1 outside."""
+    return (~box_inside(shape, box)).long().unsqueeze(0).repeat(n, *([1] * len(shape)))
+
+
+# ---- diff mask ------------------------------------------------------------------------------------------------------------------
+def diff_mask_k(topk, M):
+    """the definition's count (oracle.train_step.create_mask_v1): max(int(topk * M), 1) in double."""
+    return max(int(topk * M), 1)
+
+
+def exact_knowledge(N, H, W, scale, gen, ties=None):
+    """knowledge >= 0 [N, H, W] of multiples of 2^-10 whose scale x scale cell sums are T * 2^-10 with T = 2^14 + a permutation of
+    0..M-1 per sample: every partial sum is a multiple of 2^-10 below 2^7 (17 significant bits), so the pooled mean is exact in fp32 in any
+    summation order and the pooled values of a sample are distinct.  ties = (k, count): `count` further cells of each sample are given
+    the k-th largest value."""
+    PH, PW = H // scale, W // scale
+    M, q = PH * PW, scale * scale
+    assert M <= 2 ** 16 and q == 16
+    T = torch.stack([torch.randperm(M, generator=gen) for _ in range(N)]) + 2 ** 14
+    if ties is not None:
+        k, count = ties
+        for n in range(N):
+            order = T[n].argsort(descending=True)
+            T[n, order[k:k + count]] = int(T[n, order[k - 1]])
+    px = torch.randint(0, 1024, (N, M, q), generator=gen)
+    px[:, :, 0] = T - px[:, :, 1:].sum(2)
+    assert int(px.min()) >= 0
+    kn = px.reshape(N, PH, PW, scale, scale).permute(0, 1, 3, 2, 4).reshape(N, H, W)
+    return kn.double().mul(2.0 ** -10).float()
+
+
+def diff_mask_ref(p1, p2, knowledge, scale, k):
+    """(p1 != p2) OR the cells whose pooled value is >= the k-th largest of their sample (all ties at that value included), fp64 pooling."""
+    if knowledge.dim() == 4:
+        n, d, h, w = knowledge.shape
+        return diff_mask_ref(p1.reshape(n, d * h, w), p2.reshape(n, d * h, w), knowledge.reshape(n, d * h, w), scale, k).reshape(n, d, h, w)
+    n = knowledge.shape[0]
+    pooled = F.avg_pool2d(_c(knowledge).unsqueeze(1), scale).squeeze(1).clamp_min(0)
+    thr = pooled.reshape(n, -1).topk(k, dim=1).values[:, -1]
+    sel = (pooled >= thr.view(n, 1, 1)).repeat_interleave(scale, 1).repeat_interleave(scale, 2)
+    return (sel | (p1 != p2)).float()
+
+
+# ---- test inputs shared by tests/test_plumbing_kernels_gpu.py and tests/test_kernel_ref_cpu.py -----------------------------------
+LOSS_SHAPES = {"2d_ragged": (3, 4, (37, 50)),              # P % 4 = 2: the scalar KL path, a ragged last wave
+               "3d_c2": (2, 2, (9, 13, 20)),               # the C = 2 instances, P % 4 = 0: the quads path
+               "2d_two_trips": (3, 4, (211, 209)),         # 132 297 pixels > 512 * 256: a second grid-stride trip for some threads only
+               "3d_c2_offset": (2, 2, (8, 12, 20))}        # P % 4 = 0, logits one float into their buffer: the scalar path again
+
+
+def loss_inputs(name):
+    """CPU inputs of a loss case (tests/test_kernel_ref_cpu.py asserts their near-tie share)."""
+    N, C, sp = LOSS_SHAPES[name]
+    g = torch.Generator().manual_seed(sum(map(ord, name)))
+    l1, l2 = torch.randn(N, C, *sp, generator=g) * 2, torch.randn(N, C, *sp, generator=g) * 2
+    # planted exact ties of the largest logit: two classes (40 pixels per head), three classes (C = 4: 24 pixels): the first index wins
+    P = l1[0, 0].numel()
+    for lg, off in ((l1, 0), (l2, 7)):
+        flat = lg.reshape(N, C, P)
+        for j in range(40):
+            n, px = j % N, (off + 997 * j) % P
+            top = flat[n, :, px].max() + 1.0
+            flat[n, C - 1, px] = top
+            flat[n, (j % (C - 1)), px] = top
+        if C == 4:
+            for j in range(24):
+                n, px = j % N, (off + 3 + 1013 * j) % P
+                top = flat[n, :, px].max() + 0.5
+                flat[n, 1:, px] = top
+    ta, tb = torch.randint(0, C, (N, *sp), generator=g), torch.randint(0, C, (N, *sp), generator=g)
+    mask = (torch.rand(N, *sp, generator=g) > 0.4).long()
+    t1 = torch.softmax(torch.randn(N, C, *sp, generator=g), 1)
+    t2 = torch.softmax(torch.randn(N, C, *sp, generator=g), 1)
+    t2.reshape(N, C, P)[:, 0, ::5] = 0.0                   # targets with exact zeros: the t > 0 guard of the KL term
+    t2 = t2 / t2.sum(1, keepdim=True)                      # ... still summing to 1 over the classes, as the kernel's KL gradient p - t assumes
+    return dict(N=N, C=C, sp=sp, l1=l1, l2=l2, ta=ta, tb=tb, mask=mask, t1=t1, t2=t2)
+
+
+def spiral(H, W, cut=None):
+    """a one-pixel-wide rectangular spiral walked inwards from the top-left corner, one blank pixel between its arms: ONE component under
+    8-connectivity, with a long union-find chain.  cut = fraction of the path at which one pixel of a straight stretch is cleared: two
+    components (the arms are two pixels apart, nothing else links them)."""
+    im = torch.zeros(H, W, dtype=torch.int64)
+    inside = lambda y, x: 0 <= y < H and 0 <= x < W
+    y, x, dy, dx = 0, 0, 0, 1
+    im[0, 0] = 1
+    path = [(0, 0)]
+    while True:
+        for _ in range(2):
+            ny, nx, fy, fx = y + dy, x + dx, y + 2 * dy, x + 2 * dx
+            if inside(ny, nx) and im[ny, nx] == 0 and (not inside(fy, fx) or im[fy, fx] == 0):
+                break
+            dy, dx = dx, -dy                               # turn right
+        else:
+            break
+        y, x = ny, nx
+        im[y, x] = 1
+        path.append((y, x))
+    if cut is not None:
+        i = int(cut * len(path))
+        while not (path[i - 1][0] == path[i + 1][0] or path[i - 1][1] == path[i + 1][1]):
+            i += 1
+        im[path[i]] = 0
+    return im
+
+
+def serpentine(H, W):
+    """rows 0, 2, 4, .. full (runs of W pixels), joined alternately at the right and the left end: one component."""
+    im = torch.zeros(H, W, dtype=torch.int64)
+    im[0::2] = 1
+    for j, y in enumerate(range(1, H - 1, 2)):
+        im[y, W - 1 if j % 2 == 0 else 0] = 1
+    return im

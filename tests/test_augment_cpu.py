@@ -113,7 +113,7 @@ def test_new_entry_points_load_and_bind(tmp_path):
         assert fn.restype is ctypes.c_int
         with pytest.raises(_lib.ChapError, match="null"):       # argument check, no launch
             _lib.call(name, st(), 0)
-    assert _lib.lib().chap_abi_version() == 7
+    assert _lib.lib().chap_abi_version() == _lib.ABI_VERSION == 9
     pairs = {"chap_augment2d_record": _lib.Augment2dRecord, "chap_augment2d_params": _lib.Augment2dParams,
              "chap_augment3d_record": _lib.Augment3dRecord, "chap_augment3d_params": _lib.Augment3dParams}
     c = tmp_path / "sz.c"

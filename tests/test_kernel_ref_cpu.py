@@ -296,3 +296,290 @@ def test_mutation_g_dw_and_db_missing_one_blocks_partial_row():
     db = gm.sum((0, 2, 3))
     assert fails("mut g db", db, rw["db"], kr.wgrad_bound(rw, which="db"))
     assert relerr(got, ref) >= WTOL[dtype] and relerr(db, rw["db"]) >= WTOL[dtype]     # (rejected at this size)
+
+
+# ==== plumbing kernels (losses, VAT / BCP helpers, RNG, diff mask, largest component, SGD) ==========================================
+import numpy as np
+
+from oracle import train_step as ots
+
+LTOL, GTOL = 1e-5, 1e-4                                   # tests/test_kernels_bwd_gpu.py::test_losses_vs_oracle: loss values, gradients
+STOL = 1e-6                                                # ::test_lcc_diffmask_vat_helpers_sgd: SGD parameters and momenta
+
+
+def test_loss_restatements_equal_fp64_autograd():
+    for name, kw in (("2d_ragged", dict(w=(0.5, 1.0))), ("3d_c2", dict(w=(1.0, 0.5))), ("3d_c2_offset", dict(w=(0.75, 0.25), plain=True))):
+        c = kr.loss_inputs(name)
+        lo = c["l1"].double().requires_grad_(True)
+        plain = kw.get("plain", False)
+        m = torch.ones_like(c["mask"]) if plain else c["mask"]
+        tb = c["ta"] if plain else c["tb"]
+        wa, wb = kw["w"]
+        li, lp, tot = ots.mix_loss(lo, c["ta"], tb, m.double(), l_weight=wa, u_weight=wb)
+        (tot * 0.25).backward()                            # weights and scale exact in fp32, as the kernel receives them
+        r = kr.mix_loss_ref(c["l1"], c["ta"], None if plain else tb, None if plain else m, wa, wb, gscale=0.25)
+        assert close(r["loss"], torch.stack([li, lp, tot]).detach()) and close(r["dlogits"], lo.grad)
+        # k_dice / k_ce: loss_k = w_k (kd Dice_k + kc CE_k)
+        lo = c["l1"].double().requires_grad_(True)
+        soft = F.softmax(lo, 1)
+        parts = []
+        for t, mk, w in ((c["ta"], m.double(), wa), (tb, 1.0 - m.double(), wb)):
+            ce = (F.cross_entropy(lo, t, reduction="none") * mk).sum() / (mk.sum() + 1e-16)
+            parts.append(w * (0.3 * ots.dice_loss_bcp(soft, t, mk, c["C"]) + 1.7 * ce))
+        (parts[0] + parts[1]).backward()
+        r = kr.mix_loss_ref(c["l1"], c["ta"], tb, m, wa, wb, k_dice=0.3, k_ce=1.7)
+        assert abs(float(r["loss"][2] - (parts[0] + parts[1]).detach())) < 1e-6 * float(r["loss"][2])      # 0.3f, 1.7f: the fp32 scalars the kernel gets
+        assert (r["dlogits"] - lo.grad).abs().max() < 1e-6 * lo.grad.abs().max()
+        # pseudo block
+        pr = kr.pseudo_ref(c["l1"], c["l2"])
+        s1, s2, a1, a2, kn = ots.pseudo_block(c["l1"].double(), c["l2"].double())
+        assert close(pr["soft1"], s1) and close(pr["soft2"], s2) and close(pr["knowledge"], kn)
+        assert torch.equal(pr["arg1"], a1) and torch.equal(pr["arg2"], a2)
+        # the two distances, accumulated onto a prior loss value
+        for mode, fn in (("kl", ots.kl_two_heads), ("dice", ots.dice_two_heads)):
+            la, lb = c["l1"].double().requires_grad_(True), c["l2"].double().requires_grad_(True)
+            d = fn((la, lb), (c["t1"].double(), c["t2"].double()))
+            (d * 0.75).backward()
+            r = kr.kl_ref((c["l1"], c["l2"]), (c["t1"], c["t2"]), mode, gscale=0.75, prior=0.25)
+            assert abs(float(r["loss"]) - 0.25 - float(d.detach())) < 1e-12
+            # the kernel's KL gradient gs/total (p - t) is the derivative for targets that sum to 1 over the classes: these do to fp32 rounding
+            tol = 1e-12 if mode == "dice" else 4 * kr.U32
+            assert (r["g"][0] - la.grad).abs().max() <= tol * la.grad.abs().max() and (r["g"][1] - lb.grad).abs().max() <= tol * lb.grad.abs().max()
+
+
+@pytest.mark.parametrize("name", list(kr.LOSS_SHAPES))
+def test_near_tie_share_of_the_pseudo_block_inputs(name):
+    """the GPU test leaves pixels out of the argmax comparison only where fp64 cannot decide it: none on these inputs (cap 0.01 %), while
+    the planted exact ties (gap 0) stay in."""
+    c = kr.loss_inputs(name)
+    r = kr.pseudo_ref(c["l1"], c["l2"])
+    assert float(r["near"].double().mean()) <= kr.NEAR_TIE_CAP and int(r["near"].sum()) == 0
+    top = r["soft1"].topk(2, dim=1).values
+    assert int((top[:, 0] == top[:, 1]).sum()) >= 40       # exact ties are present and are compared
+
+
+def test_helper_restatements_equal_the_oracle():
+    g = gen(20)
+    x = torch.randn(3, 1, 9, 13, generator=g).double()
+    assert close(kr.l2_normalize_ref(x)[0], ots.l2_normalize(x))
+    d, m = torch.randn(3, 1, 9, 13, generator=g).double(), (torch.rand(3, 1, 9, 13, generator=g) > 0.5).double()
+    assert close(kr.perturb_ref(x, d, 6.0, m)[0], x + 6.0 * m * d) and close(kr.perturb_ref(x, d, 0.5, None, True)[0], x + 0.5 * torch.sign(d))
+    p, gr, mo = (torch.randn(1003, generator=g).double() for _ in range(3))
+    params, moms = [p.clone()], [mo.clone()]
+    ots.sgd_step(params, [gr], moms, 0.5, 0.75, 0.125)       # scalars exact in fp32
+    p2, _, m2, _ = kr.sgd_ref(p, gr, mo, 0.5, 0.75, 0.125)
+    assert close(p2, params[0]) and close(m2, moms[0])
+    a, b = torch.randn(6, 4, 3, 3, generator=g).double(), torch.randn(6, 4, 3, 3, generator=g).double()
+    sim = F.cosine_similarity(a.reshape(6, -1), b.reshape(6, -1), dim=1, eps=0)
+    assert close(kr.grad_sim_ref(a, b, torch.zeros(6), 0.0)[0], sim)
+    assert close(kr.grad_sim_ref(a, b, torch.ones(6), 0.5)[0], 0.5 + 0.5 * sim)
+    # boxes: generate_mask's zero box
+    mask, lm = ots.box_masks(2, 37, 50, 5, 9)
+    box = (5, 9, int(37 * 2 / 3), int(50 * 2 / 3))
+    assert torch.equal(kr.box_mask_ref(2, (37, 50), box), lm.long())
+    u, v = torch.rand(2, 1, 37, 50, generator=g), torch.rand(2, 1, 37, 50, generator=g)
+    assert torch.equal(kr.box_mix_ref(u, v, box), u * mask + v * (1 - mask))
+    mask3, lm3 = ots.box_masks_3d(2, 5, 9, 13, 1, 2, 3)
+    assert torch.equal(kr.box_mask_ref(2, (5, 9, 13), (1, 2, 3, 3, 6, 8)), lm3.long())
+    # diff mask: the exact construction makes fp32 and fp64 pooling agree, so the oracle's fp32 mask is the reference's
+    for shape, topk in (((3, 40, 40), 0.29), ((2, 60, 96), 0.35), ((2, 6, 20, 24), 0.1)):
+        H, W = (shape[1], shape[2]) if len(shape) == 3 else (shape[1] * shape[2], shape[3])
+        kn = kr.exact_knowledge(shape[0], H, W, 4, g).reshape(shape)
+        pooled = F.avg_pool2d(kn.reshape(shape[0], 1, H, W), 4)
+        assert torch.equal(pooled.double(), F.avg_pool2d(kn.double().reshape(shape[0], 1, H, W), 4))
+        assert all(len(set(row.tolist())) == row.numel() for row in pooled.reshape(shape[0], -1))         # distinct
+        p1 = torch.randint(0, 4, shape, generator=g)
+        p2 = torch.where(torch.rand(shape, generator=g) < 0.02, (p1 + 1) % 4, p1)
+        k = kr.diff_mask_k(topk, pooled[0].numel())
+        assert torch.equal(kr.diff_mask_ref(p1, p2, kn, 4, k), ots.create_mask_v1(p1, p2, kn, 4, topk))
+    assert [kr.diff_mask_k(t, m) for t, m in ((0.29, 100), (0.35, 360), (0.7, 360), (1e-6, 100), (1.0, 100))] == [28, 125, 251, 1, 100]
+    assert [int(np.float32(t) * np.float32(m)) for t, m in ((0.29, 100), (0.35, 360), (0.7, 360))] == [29, 126, 252]       # the float product
+
+
+def test_u01_is_the_splitmix64_finalizer():
+    """u01(seed, i) = the top 24 bits of splitmix64's (i + 1)-th output from state `seed`: the published first outputs for seed 0."""
+    assert [int(v) for v in kr.u01_np(0, np.arange(2))] == [0xE220A8397B1DCDAF >> 40, 0x6E789E6AA1B965F4 >> 40]
+    for seed, sd in ((77, None), (77, 0), (77, 5), ((1 << 64) - 3, 1 << 62), (123, -1)):
+        a = kr.u01_np(seed, np.arange(70000), sd)
+        assert np.array_equal(a, kr.u01_int(seed, 70000, sd).numpy()) and 0 <= a.min() and a.max() < 1 << 24
+    assert np.array_equal(kr.u01_np(77, np.arange(100), None), kr.u01_np(77, np.arange(100), 0))
+    assert not np.array_equal(kr.u01_np(77, np.arange(100), 0), kr.u01_np(77, np.arange(100), 5))
+    keep = kr.keep_mask_ref(5, 1 << 16, 0.3)
+    assert abs(float(keep.float().mean()) - 0.7) < 1e-2 and bool((kr.keep_mask_ref(5, 100, 0.0) == 1).all()) and bool((kr.keep_mask_ref(5, 100, 1.0) == 0).all())
+    cm = kr.chan_mask_ref(5, 1000, 0.3)
+    assert set(cm.tolist()) == {0.0, float(torch.tensor(1.0) / (torch.tensor(1.0) - torch.tensor(0.3)))}
+    v, b = kr.rand_uniform_ref(123, 1000, -0.5, 0.5)
+    assert float(v.min()) >= -0.5 and float(v.max()) < 0.5 and float(b.max()) <= 2.0 ** -23
+
+
+# ---- an emulated CORRECT loss kernel: fp32 arithmetic, one partial row per 256 pixels, another summation order -------------------
+def _emulate_mix(c, w=(0.5, 1.0), drop_tail=False, drop_row=None, msum_both=False, smear_last=False):
+    lg, C = c["l1"], c["C"]
+    N, P = lg.shape[0], lg[0, 0].numel()
+    z = lg.reshape(N, C, P)
+    p = torch.softmax(z, 1)                                # fp32
+    lse = torch.logsumexp(z, 1)
+    mk = [c["mask"].reshape(N, P).float(), 1.0 - c["mask"].reshape(N, P).float()]
+    ts = [F.one_hot(t.reshape(N, P), C).permute(0, 2, 1).float() for t in (c["ta"], c["tb"])]
+    rows = []
+    for k in range(2):
+        cols = [(lse - (ts[k] * z).sum(1)) * mk[k]] + [p[:, i] * ts[k][:, i] * mk[k] for i in range(C)] + [p[:, i] * p[:, i] * mk[k] for i in range(C)] \
+            + [ts[k][:, i] * mk[k] for i in range(C)] + [mk[k]]
+        rows.append(torch.stack([v.reshape(-1) for v in cols], 1))          # [N * P, NA], pixel-major as the kernel walks them
+    per_px = torch.cat(rows, 1)
+    total = N * P
+    if drop_tail:
+        per_px = per_px[:total - total % 256]
+    pad = (-per_px.shape[0]) % 256
+    blocks = F.pad(per_px, (0, 0, 0, pad)).reshape(-1, 256, per_px.shape[1]).flip(1).sum(1)      # a block's row, summed back to front
+    if drop_row is not None:
+        blocks[drop_row] = 0
+    acc = blocks.double().sum(0).float().reshape(2, -1)
+    if msum_both:
+        acc[:, -1] = acc[:, -1].sum()
+    s, kd, kc = torch.tensor(1e-10), 0.5, 0.5
+    part, dz, dp = [], torch.zeros_like(p), torch.zeros_like(p)
+    for k in range(2):
+        a = acc[k]
+        I, Z, Y = a[1:1 + C], a[1 + C:1 + 2 * C], a[1 + 2 * C:1 + 3 * C]
+        den = Z + Y + s
+        dice = (1.0 - (2.0 * I + s) / den).sum() / C * w[k]
+        ce = w[k] * a[0] / (a[-1] + 1e-16)
+        part.append(kd * dice + kc * ce)
+        kce = w[k] * mk[k] / (a[-1] + 1e-16)
+        dz = dz + kce.unsqueeze(1) * (p - ts[k])
+        dp = dp + (w[k] / C) * mk[k].unsqueeze(1) * (-2.0 * ts[k] / den.view(1, C, 1) + ((2.0 * I + s) * 2.0 / (den * den)).view(1, C, 1) * p)
+    dl = kc * dz + kd * p * (dp - (dp * p).sum(1, keepdim=True))
+    if smear_last:
+        dl[:, :, -1] = dl[:, :, -2]
+    return acc, torch.stack([part[0], part[1], part[0] + part[1]]), dl.reshape(lg.shape)
+
+
+@pytest.fixture(scope="module")
+def two_trips():
+    c = kr.loss_inputs("2d_two_trips")
+    return c, kr.mix_loss_ref(c["l1"], c["ta"], c["tb"], c["mask"], 0.5, 1.0)
+
+
+def test_emulated_correct_loss_kernels_pass(two_trips):
+    c, r = two_trips
+    acc, loss, dl = _emulate_mix(c)
+    kr.check("acc", acc, r["acc"], r["acc_b"], "ka")
+    kr.check("loss", loss, r["loss"], r["loss_b"], "k")
+    kr.check("dlogits", dl, r["dlogits"], r["dlogits_b"])
+    for name in ("2d_ragged", "3d_c2"):                    # and the small shapes; softmax / knowledge / the distances in plain fp32
+        c = kr.loss_inputs(name)
+        r = kr.mix_loss_ref(c["l1"], c["ta"], c["tb"], c["mask"], 0.5, 1.0)
+        acc, loss, dl = _emulate_mix(c)
+        kr.check("acc", acc, r["acc"], r["acc_b"], "ka"), kr.check("loss", loss, r["loss"], r["loss_b"], "k"), kr.check("dlogits", dl, r["dlogits"], r["dlogits_b"])
+        pr = kr.pseudo_ref(c["l1"], c["l2"])
+        s1, s2, a1, a2, kn = ots.pseudo_block(c["l1"], c["l2"])
+        kr.check("soft1", s1, pr["soft1"], pr["soft1_b"]), kr.check("knowledge", kn, pr["knowledge"], pr["knowledge_b"], "ndhw")
+        assert torch.equal(a1, pr["arg1"]) and torch.equal(a2, pr["arg2"])
+        for mode, fn in (("kl", ots.kl_two_heads), ("dice", ots.dice_two_heads)):
+            la, lb = c["l1"].clone().requires_grad_(True), c["l2"].clone().requires_grad_(True)
+            d = fn((la, lb), (c["t1"], c["t2"]))
+            (d * 0.7).backward()
+            kr_ = kr.kl_ref((c["l1"], c["l2"]), (c["t1"], c["t2"]), mode, gscale=0.7, prior=0.25)
+            kr.check("dist loss", (d.detach() + 0.25).reshape(1), kr_["loss"], kr_["loss_b"], "k")
+            kr.check("dist g0", la.grad, kr_["g"][0], kr_["g_b"][0]), kr.check("dist g1", lb.grad, kr_["g"][1], kr_["g_b"][1])
+
+
+def test_emulated_correct_helpers_pass():
+    g = gen(21)
+    x = torch.randn(3, 6149, generator=g)
+    x[1] = 0
+    ref, b = kr.l2_normalize_ref(x)
+    kr.check("l2", x / (x.reshape(3, -1, 11).pow(2).sum(2).sum(1).sqrt().view(3, 1) + 1e-8), ref, b, "np")
+    n = 1003
+    p, gr, g2, mo = (torch.randn(n, generator=g) for _ in range(4))
+    f = lambda v: torch.tensor(v, dtype=torch.float32)
+    gg = (gr + g2) * f(1 / 3) + f(1e-4) * p
+    m2 = f(0.9) * mo + gg
+    p2, e_p, mr, e_m = kr.sgd_ref(p, gr, mo, 0.013, 0.9, 1e-4, 1 / 3, g2)
+    kr.check("sgd p", p - f(0.013) * m2, p2, e_p, "i"), kr.check("sgd m", m2, mr, e_m, "i")
+    d = torch.randn(n, generator=g)
+    ref, b = kr.perturb_ref(p, d, 6.0, (mo > 0).float())
+    kr.check("perturb", p + f(6.0) * (mo > 0).float() * d, ref, b, "i")
+    a, bb, s0 = torch.randn(6, 144, generator=g), torch.randn(6, 144, generator=g), torch.randn(6, generator=g)
+    ref, b = kr.grad_sim_ref(a, bb, s0, 0.9)
+    kr.check("grad_sim", f(0.9) * s0 + (1 - f(0.9)) * F.cosine_similarity(a.double(), bb.double(), dim=1).float(), ref, b, "c")
+
+
+# ---- mutations of the plumbing kernels; the old whole-tensor verdict (relerr < tolerance) is recorded next to each ----------------
+def test_mutation_h_loss_accumulators_missing_the_last_partial_block(two_trips):
+    c, r = two_trips                                       # 132 297 pixels: the last 201 lost
+    acc, loss, dl = _emulate_mix(c, drop_tail=True)
+    assert fails("mut h acc", acc, r["acc"], r["acc_b"]) and fails("mut h loss", loss, r["loss"], r["loss_b"])
+    assert relerr(loss, r["loss"]) >= LTOL                 # (201 of 132 297 pixels: 1.5e-3 of every sum -- the old check rejects it too at this size)
+
+
+def test_mutation_i_loss_accumulators_missing_one_blocks_row(two_trips):
+    c, r = two_trips
+    acc, loss, dl = _emulate_mix(c, drop_row=300)
+    assert fails("mut i acc", acc, r["acc"], r["acc_b"]) and fails("mut i loss", loss, r["loss"], r["loss_b"])
+    assert fails("mut i dlogits", dl, r["dlogits"], r["dlogits_b"])
+    assert relerr(loss, r["loss"]) >= LTOL and relerr(dl, r["dlogits"]) >= GTOL     # (rejected at this size: one row of 517 is 2e-3 of every total)
+
+
+def test_mutation_j_dlogits_last_pixel_of_each_sample_gets_its_neighbours_value(two_trips):
+    c, r = two_trips
+    acc, loss, dl = _emulate_mix(c, smear_last=True)
+    assert fails("mut j", dl, r["dlogits"], r["dlogits_b"])
+    assert relerr(dl, r["dlogits"]) >= GTOL                # (rejected: a gradient element is of the size of the largest one)
+
+
+def test_mutation_k_msum_taken_over_both_parts(two_trips):
+    c, r = two_trips
+    acc, loss, dl = _emulate_mix(c, msum_both=True)
+    assert fails("mut k acc", acc, r["acc"], r["acc_b"]) and fails("mut k loss", loss, r["loss"], r["loss_b"]) and fails("mut k dl", dl, r["dlogits"], r["dlogits_b"])
+    assert relerr(loss, r["loss"]) >= LTOL
+
+
+def test_mutations_l_m_diff_mask_count_off_by_one_and_ties_dropped():
+    g = gen(22)
+    kn = kr.exact_knowledge(3, 40, 40, 4, g)
+    p1 = torch.randint(0, 4, (3, 40, 40), generator=g)
+    ref = kr.diff_mask_ref(p1, p1, kn, 4, kr.diff_mask_k(0.29, 100))
+    off = kr.diff_mask_ref(p1, p1, kn, 4, int(np.float32(0.29) * np.float32(100)))           # the float product's count: 29
+    assert int((ref != off).sum()) == 3 * 16               # one 4x4 cell per sample
+    assert relerr(off, ref) == 1.0                         # (a mask: any wrong pixel is a whole-tensor error of 1; the old test only ran topk = 0.1)
+    # ties at the threshold: the k-th value occurs 4 times; a select that keeps exactly k cells drops three of them
+    kn = kr.exact_knowledge(3, 40, 40, 4, g, ties=(28, 3))
+    ref = kr.diff_mask_ref(p1, p1, kn, 4, 28)
+    pooled = F.avg_pool2d(kn.unsqueeze(1), 4).reshape(3, -1)
+    idx = pooled.topk(28, dim=1).indices
+    dropped = torch.zeros(3, 100).scatter_(1, idx, 1.0).reshape(3, 10, 10).repeat_interleave(4, 1).repeat_interleave(4, 2)
+    assert int(ref.sum()) == 3 * 31 * 16 and int((ref != dropped).sum()) == 3 * 3 * 16
+
+
+def test_mutation_n_one_union_missing_cuts_the_spiral():
+    whole, cut = kr.spiral(67, 131), kr.spiral(67, 131, cut=0.4)
+    ref = ots.largest_cc(whole.unsqueeze(0), 2)
+    assert torch.equal(ref[0], whole)                      # one component: all of it is kept
+    got = ots.largest_cc(cut.unsqueeze(0), 2)              # what a labelling that misses the union at the cut keeps: the larger arm only
+    lost = int((got != ref).sum())
+    assert lost > 1000 and not torch.equal(got, ref)
+    # the smooth blobs of the old test hold no component that hangs on a single union
+
+
+def test_mutation_o_keep_bytes_of_the_last_partial_group_shifted():
+    n = 65539                                              # 4096 full groups and 3 bytes
+    ref = kr.keep_mask_ref(77, n, 0.3)
+    got = ref.clone()
+    got[n - 3:] = kr.keep_mask_ref(77, n + 1, 0.3)[n - 2:]  # byte i of the tail drawn from index i + 1
+    assert not torch.equal(got, ref)
+    assert abs(float(got.float().mean()) - 0.7) < 1e-2     # ACCEPTED by the old check (the mean of the mask)
+
+
+def test_mutation_p_sgd_tail_not_updated():
+    g = gen(23)
+    n = 1003
+    p, gr, mo = (torch.randn(n, generator=g) for _ in range(3))
+    f = lambda v: torch.tensor(v, dtype=torch.float32)
+    m2 = f(0.9) * mo + (gr + f(1e-4) * p)
+    got = p - f(0.01) * m2
+    got[n - n % 4:] = p[n - n % 4:]
+    p2, e_p, _, _ = kr.sgd_ref(p, gr, mo, 0.01, 0.9, 1e-4)
+    assert fails("mut p", got, p2, e_p)
+    assert relerr(got, p2) >= STOL                         # (rejected at lr = 0.01: the step is 1e-2 of a parameter)
