@@ -5,6 +5,8 @@ from the operands the kernel multiplies -- the lazy transform rounded where the 
 operand type -- together with the sums of absolute terms the bound needs.  `bound` turns those into a per-element bound on
 |kernel - reference|; `check` compares and names the worst element.  The second half restates the plumbing kernels (losses, VAT / BCP
 helpers, the counter-based RNG, the perturbation mask, SGD, GradSim) in the same way; what is an integer, a mask or a copy is exact.
+The third part does the same for the evaluation kernels (ensemble_argmax, the sliding-window accumulate / finalize), the channel-drop kernels,
+bn_finalize / bn_eval_affine, the channel sums and the layout converters.
 
 Constants, fixed before any GPU run and never fitted to observed errors:
   U32 = 2^-24, U_BF16 = 2^-8   unit roundoff (round to nearest) of an fp32 / bf16 value (24 / 8 significant bits).
@@ -810,3 +812,369 @@ def serpentine(H, W):
     for j, y in enumerate(range(1, H - 1, 2)):
         im[y, W - 1 if j % 2 == 0 else 0] = 1
     return im
+
+
+# ==== evaluation, channel-drop, BatchNorm-finalize and layout kernels ================================================================
+# Chains (every bound below was written before the first GPU run):
+#   softmax_c (loss.hip)   __expf(x) compiles to v_exp_f32(fl(x * fl(log2 e))) (clang's __clang_hip_math.h): the subtract, the float constant and
+#                          the product each put a relative d U32 (d = |z - m|) on the exponential; then the exp, C - 1 adds, one reciprocal, one
+#                          product.  v_exp_f32 returns 0 for a result below the smallest normal number.
+#   bn_finalize            fp32 slot values summed in fp64 (relative 2^-53 per add: the term `ulp64`), then the fp32 roundings counted below.
+#   channel sums           a thread's pixel loop, the shuffle / LDS reduction: an fp32 chain of at most the pixels one result sums.
+#   channel_drop           one block: fp32 chains over nchunk and over C, then the short elementwise chain of the probability.
+# A term whose fp64 value is below EXP_UNDERFLOW may be 0 in the kernel.  v_exp_f32 has no denormal results: it returns 0 once its ROUNDED argument
+# fl(x * fl(log2 e)) is below -126, and that argument is off by up to 3 d U32 log2 e = 2^-22.6 d from the true one (d <= 88 here: 2^-16): the true term is then
+# below 2^(-126 + 2^-16).  2^-126 itself, the figure of a kernel with an exact argument, would leave such a term unbounded; the next power of two, 2^-125, is
+# taken -- the only place where this bound is wider than "the reference's term is below 2^-126".
+EXP_UNDERFLOW = 2.0 ** -125
+
+
+def infer_softmax_ref(logits):
+    """softmax_c over dim 1 of fp64 logits [N, C, ...], C <= 8.  Returns dict(p, e_p):
+      e_p = (max(EW, (C + 2) U32) + 3 d U32) p + (2^-125 where exp(z - m) < 2^-125: EXP_UNDERFLOW above says why not 2^-126)."""
+    z = logits
+    C = z.shape[1]
+    m = z.amax(1, keepdim=True)
+    d = (z - m).abs()
+    ex = torch.exp(z - m)
+    s = ex.sum(1, keepdim=True)
+    p = ex / s
+    e = (max(EW, (C + 2) * U32) + 3 * d * U32) * p
+    return dict(p=p, e_p=e + torch.where(ex < EXP_UNDERFLOW, EXP_UNDERFLOW, 0.0))
+
+
+def label_ref(p, e_p):
+    """(first maximal index over dim 1, near): near = the two largest values differ by more than 0 (an exact tie of the reference is an exact
+    tie of the kernel for these kernels' inputs: the first index wins) and by no more than the sum of their bounds."""
+    if p.shape[1] == 1:
+        z = torch.zeros(p[:, 0].shape, dtype=torch.int64, device=p.device)
+        return z, z.bool()
+    top = p.topk(2, dim=1)
+    gap = top.values[:, 0] - top.values[:, 1]
+    thr = e_p.gather(1, top.indices).sum(1)
+    return p.argmax(1), (gap > 0) & (gap <= thr)
+
+
+def ensemble_ref(a, b, mode):
+    """chap_ensemble_argmax: a, b fp32 logits [N, C, *sp] (the unused head may be None).  Returns dict(p, e_p, label, near).
+      model1 / model2   softmax_c of one head
+      logit_ensemble    softmax_c of fl(a + b) / 2: the add rounds once, the halving is exact.  The reference rounds the sum to fp32 as the kernel does (an
+                        fp32 add is correctly rounded, so fl of the fp64 sum IS the kernel's value) instead of carrying U32 |a + b| / 2 through the softmax
+                        as a term 2 * that on e_p: tighter, at the price that the reference shares the kernel's first operation -- a wrong add (a
+                        head read twice, a missing halving) still shows, as an error of the size of the logits
+      prob_ensemble     fl(p1 + p2) / 2: (e_p1 + e_p2) / 2 + U32 p"""
+    if mode == "model1":
+        r = infer_softmax_ref(_c(a))
+    elif mode == "model2":
+        r = infer_softmax_ref(_c(b))
+    elif mode == "logit_ensemble":
+        r = infer_softmax_ref(f32(_c(a) + _c(b)) / 2.0)
+    elif mode == "prob_ensemble":
+        r1, r2 = infer_softmax_ref(_c(a)), infer_softmax_ref(_c(b))
+        p = (r1["p"] + r2["p"]) / 2.0
+        r = dict(p=p, e_p=(r1["e_p"] + r2["e_p"]) / 2.0 + U32 * p)
+    else:
+        raise ValueError(mode)
+    r["label"], r["near"] = label_ref(r["p"], r["e_p"])
+    return r
+
+
+def window_accumulate_ref(logits, origins, score0, cnt0):
+    """chap_window_accumulate: logits [K, C, pw, ph, pd], origins [(x, y, z)] * K, score0 [C, W, H, D] and cnt0 [W, H, D] (what the buffers held).
+    Per voxel the covering patches in patch order k: value = prior + sum_k p_k, one fp32 add per patch.
+    Returns dict(score, score_b, cnt, covered): score_b = sum_k e_p,k + n_cover U32 (|prior| + sum_k p_k); 0 where no patch covers (the voxel
+    must be left as it was); cnt exact."""
+    lg = _c(logits)
+    prior = _c(score0, lg)
+    K, C, pw, ph, pd = lg.shape
+    sm = infer_softmax_ref(lg)
+    sp, se, n = torch.zeros_like(prior), torch.zeros_like(prior), torch.zeros_like(prior[0])
+    for k, (x, y, z) in enumerate(origins):
+        sl = (slice(x, x + pw), slice(y, y + ph), slice(z, z + pd))
+        sp[(slice(None),) + sl] += sm["p"][k]
+        se[(slice(None),) + sl] += sm["e_p"][k]
+        n[sl] += 1
+    return dict(score=prior + sp, score_b=se + n * U32 * (prior.abs() + sp), cnt=_c(cnt0, lg) + n, covered=n > 0)
+
+
+def window_finalize_ref(score, cnt, e_score=None):
+    """chap_window_finalize: v = fl(score / cnt) with bound e_score / cnt + U32 |v|; label = the first maximal index (near as label_ref).  Where cnt == 0
+    the quotient is not finite (0 / 0 = NaN): `empty` names those voxels, their value and bound are set to 0 here and the caller asserts them apart."""
+    s, c = _c(score), _c(cnt, score).unsqueeze(0)
+    empty = (c == 0).squeeze(0)
+    cs = torch.where(c == 0, torch.ones_like(c), c)
+    v = torch.where(c == 0, torch.zeros_like(s), s / cs)
+    b = (torch.zeros_like(s) if e_score is None else _c(e_score, s)) / cs + U32 * v.abs()
+    b = torch.where(c == 0, torch.zeros_like(b), b)
+    label, near = label_ref(v.unsqueeze(0), b.unsqueeze(0))
+    return dict(score=v, score_b=b, label=label[0], near=near[0] & ~empty, empty=empty)
+
+
+def bn_finalize_ref(slots, nslots, C, Clog, count, shift, gamma_, beta, rm, rv, momentum, eps):
+    """chap_bn_finalize.  slots: fp32 [>= nslots, 2 (S | Q), Clog]; rows >= nslots are not read.  S, Q = the fp64 totals over the slots in use and over the
+    Clog / C sub-lattice rows; n = the fp32 count.
+      ms = S / n;  var = max(Q / n - ms^2, 0)                                   fp64
+      mean = fl(shift + ms)   invstd = fl(1 / sqrt(var + eps))                  one fp32 rounding each
+      scale = fl(gamma invstd)                                                  one more
+      shift' = beta - mean scale                                                product and subtract, fused or not: U32 (|mean scale| + |shift'|)
+      running_mean' = fl(fl(fl(1 - mom) rm) + fl(mom mean))                     fl(1 - mom) is the kernel's own value (a correctly rounded subtract);
+      running_var'  = the same with unb = fl(var n / (n - 1)) (n > 1; else var)  two products and an add, fused or not: U32 (|a| + |b| + |sum|)
+    Every bound also carries `ulp64`, the fp64 summation error of the totals (2^-53 per add on sum |slot value|), through the partial derivatives -- it matters
+    only where var cancels.  Returns dict name -> (value, bound); running statistics only when momentum > 0 and rm is given."""
+    sl = _c(slots)[:nslots]
+    n = float(torch.tensor(float(count), dtype=torch.float32))
+    nsub = Clog // C
+    fold = lambda t: t.reshape(nsub, C).sum(0)
+    S, Q = fold(sl[:, 0].sum(0)), fold(sl[:, 1].sum(0))
+    terms = nslots * nsub + 4
+    dS, dQ = 2.0 ** -53 * terms * fold(sl[:, 0].abs().sum(0)), 2.0 ** -53 * terms * fold(sl[:, 1].abs().sum(0))
+    ms = S / n
+    raw = Q / n - ms * ms
+    var = raw.clamp_min(0.0)
+    dvar = dQ / n + 2 * ms.abs() * dS / n + 2.0 ** -52 * (Q.abs() / n + ms * ms)
+    eps = _fp32_scalar(eps)
+    sft = _c(shift, sl) if shift is not None else torch.zeros_like(S)
+    gam, bet = _c(gamma_, sl), _c(beta, sl)
+    mean = sft + ms
+    e_mean = U32 * mean.abs() + dS / n
+    invstd = 1.0 / torch.sqrt(var + eps)
+    e_inv = U32 * invstd + 0.5 * invstd * dvar / (var + eps)
+    scale = gam * invstd
+    e_scale = gam.abs() * e_inv + U32 * scale.abs()
+    sh = bet - mean * scale
+    e_sh = scale.abs() * e_mean + mean.abs() * e_scale + U32 * ((mean * scale).abs() + sh.abs())
+    out = dict(mean=(mean, e_mean), invstd=(invstd, e_inv), scale=(scale, e_scale), shift=(sh, e_sh))
+    mom = _fp32_scalar(momentum)
+    if mom > 0 and rm is not None:
+        om = float(torch.tensor(1.0, dtype=torch.float32) - torch.tensor(mom, dtype=torch.float32))
+        unb = var * n / (n - 1.0) if n > 1.0 else var
+        e_unb = U32 * unb + dvar * (n / (n - 1.0) if n > 1.0 else 1.0)
+        for name, old, new, e_new in (("running_mean", _c(rm, sl), mean, e_mean), ("running_var", _c(rv, sl), unb, e_unb)):
+            a, b = om * old, mom * new
+            out[name] = (a + b, mom * e_new + U32 * (a.abs() + b.abs() + (a + b).abs()))
+    return out
+
+
+def bn_eval_ref(gamma_, beta, rm, rv, eps):
+    """chap_bn_eval_affine: scale = gamma rsqrtf(rv + eps), shift = beta - rm scale.
+      scale   the add (U32 on rv + eps: U32 / 2 on the root), rsqrtf (v_rsq_f32: an approximation good to one ulp = 2 U32, not a correctly rounded result), the
+              product: 4 U32 |scale|
+      shift   fused: one rounding, U32 |shift|; not fused: U32 |rm scale| + U32 |shift|: the larger (second) form is the bound; plus |rm| e_scale.
+    Returns ((scale, e_scale), (shift, e_shift))."""
+    g, b, m, v = (_c(t) for t in (gamma_, beta, rm, rv))
+    scale = g / torch.sqrt(v + _fp32_scalar(eps))
+    e_scale = 4 * U32 * scale.abs()
+    shift = b - m * scale
+    return (scale, e_scale), (shift, m.abs() * e_scale + U32 * ((m * scale).abs() + shift.abs()))
+
+
+def _chan_red(t):
+    return [0] + list(range(2, t.dim()))
+
+
+def channel_sum_ref(lazy, prior=None):
+    """chap_channel_sum: out[c] += sum over all pixels of a lazy activation.  lazy = (v, dv) of lazy_f32, [N, C, *sp].  The chain is the N * P pixels a result
+    sums (a thread's loop, the shuffles, the LDS rows; the block rows are totalled in fp64): gamma(N P) sum |v| + sum dv, then param_grad_bound for the
+    fp32 total and its += .  Returns (prior + S, bound)."""
+    v, dv = lazy
+    red = _chan_red(v)
+    S = v.sum(red)
+    b = gamma(v[:, 0].numel()) * v.abs().sum(red) + dv.sum(red)
+    return S + (_c(prior, S) if prior is not None else 0.0), param_grad_bound(S, b, prior)
+
+
+def sample_channel_sum_ref(lazy):
+    """chap_sample_channel_sum: per-sample sums [N, C] of a lazy activation, delivered as partial rows whose SUM is the contract (how the pixels are
+    dealt to the rows is not).  A row is an fp32 chain over its pixels, the caller adds the rows in fp64: gamma(P) sum |v| + sum dv.
+    Returns dict(sum, sum_b, mean, mean_b): mean = sum / P, what channel_drop consumes."""
+    v, dv = lazy
+    red = list(range(2, v.dim()))
+    P = v[0, 0].numel()
+    S = v.sum(red)
+    b = gamma(P) * v.abs().sum(red) + dv.sum(red)
+    return dict(sum=S, sum_b=b, mean=S / P, mean_b=b / P)
+
+
+def channel_drop_ref(u1, u2, B, mode, *, pool_partial=None, npix=1, grad_sim=None, comp=False, branch=0, prob_kind="sigmoid"):
+    """chap_channel_drop in fp64.  u1, u2 [U, C] uniforms; mode 'dropout2d' | 'comp_binomial' | 'scores'; pool_partial fp32 [U, nchunk, C].
+    scores with an all-zero grad_sim is dropout2d.  The chain of the probabilities (kernel order):
+      a = sum_k partial_k                 fp32 chain of nchunk: gamma(nchunk) sum |partial|
+      s = gs * (a * fl(1 / npix))         two products: |gs / npix| e_a + 2 U32 |s|
+      mean = sum_c s / C                  chain of C, a divide: (gamma(C) sum |s| + sum e_s) / C + U32 |mean|
+      q = sum_c (s - mean)^2              d = s - mean: e_d = e_s + e_mean + U32 |d|;  e_q = sum (2 |d| e_d + e_d^2) + (gamma(C) + U32) q
+      sigma = sqrtf(q / (C - 1))          divide, root: e_var = e_q / (C - 1) + U32 var;  e_sigma = e_var / (2 sigma) + U32 sigma
+      sigmoid: z = d / (sigma + 1e-8);  pr = 1 / (1 + expf(2 z))        the add, the divide, expf, the add, the divide: one U32 each, propagated
+      gauss:   z = d / (2 sigma + 1e-8); pr = 0.5 (1 + erff(z / sqrt 2)) the same with erff (|erf'| <= 2 / sqrt pi exp(-x^2)) and the rounded constant
+    masks: m = (u < q), q = 1 - pr (one more rounding) or pr: decided where |u - q| > e_q, `near` elsewhere.  mul = fl(m U C / count): exact count, the
+    product exact (integers), one divide: U32 |mul|.  An empty mask: 0 / 0, every element of it NaN.  Rows [0, B) are 1.
+    Returns dict(mode, probs, probs_b, mul1, mul1_b, mul2, mul2_b, near1, near2, nan1, nan2); mul / bounds [B + U, C]."""
+    u1, u2 = _c(u1), _c(u2, u1)
+    U, C = u1.shape
+    ones = torch.ones(B, C, dtype=torch.float64, device=u1.device)
+    full = lambda m: torch.cat((ones, m))
+    zb = torch.zeros(B + U, C, dtype=torch.float64, device=u1.device)
+    none = torch.zeros(U, C, dtype=torch.bool, device=u1.device)
+    if mode == "scores" and not bool((_c(grad_sim) != 0).any()):
+        mode = "dropout2d"
+    if mode != "scores":
+        m1 = torch.where(u1 < 0.5, 2.0, 0.0)
+        m2 = 2.0 - m1 if mode == "comp_binomial" else torch.where(u2 < 0.5, 2.0, 0.0)
+        return dict(mode=mode, probs=None, probs_b=None, mul1=full(m1), mul1_b=zb, mul2=full(m2), mul2_b=zb, near1=none, near2=none, nan1=False, nan2=False)
+    part, gs = _c(pool_partial, u1), _c(grad_sim, u1).reshape(1, C)
+    nchunk = part.shape[1]
+    inv = _fp32_scalar(1.0 / npix)
+    a = part.sum(1)
+    e_a = gamma(nchunk) * part.abs().sum(1)
+    s = gs * (a * inv)
+    e_s = gs.abs() * inv * e_a + 2 * U32 * s.abs()
+    mean = s.mean(1, keepdim=True)
+    e_mean = (gamma(C) * s.abs().sum(1, keepdim=True) + e_s.sum(1, keepdim=True)) / C + U32 * mean.abs()
+    d = s - mean
+    e_d = e_s + e_mean + U32 * d.abs()
+    q = (d * d).sum(1, keepdim=True)
+    e_q = (2 * d.abs() * e_d + e_d * e_d).sum(1, keepdim=True) + (gamma(C) + U32) * q
+    var = q / (C - 1)
+    e_var = e_q / (C - 1) + U32 * var
+    sigma = var.sqrt()
+    e_sigma = e_var / (2 * sigma).clamp_min(1e-300) + U32 * sigma
+    tiny = _fp32_scalar(1e-8)
+    if prob_kind == "gauss":
+        den = sigma * 2.0 + tiny
+        e_den = 2 * e_sigma + U32 * den
+    else:
+        den = sigma + tiny
+        e_den = e_sigma + U32 * den
+    z = d / den
+    e_z = e_d / den + z.abs() * e_den / den + U32 * z.abs()
+    if prob_kind == "gauss":
+        k = _fp32_scalar(0.70710678118654752)
+        x = z * k
+        e_x = k * e_z + 2 * U32 * x.abs()
+        er = torch.erf(x)
+        e_er = 2 / math.sqrt(math.pi) * torch.exp(-x * x) * e_x + e_x * e_x + U32 * er.abs()
+        pr = (0.5 * (1.0 + er)).clamp(0.0, 1.0)
+        e_pr = 0.5 * (e_er + U32 * (1.0 + er).abs())
+    else:
+        t = torch.exp(2.0 * z)
+        e_t = t * (2 * e_z + 4 * e_z * e_z + U32)
+        w = 1.0 + t
+        e_w = e_t + U32 * w
+        pr = 1.0 / w
+        e_pr = e_w / (w * w) + U32 * pr
+    pk, e_pk = 1.0 - pr, e_pr + U32 * (1.0 - pr).abs()
+    q1, e1 = (pr, e_pr) if (comp and branch == 1) else (pk, e_pk)
+    q2, e2 = (pr, e_pr) if (comp and branch == 0) else (pk, e_pk)
+    out = dict(mode=mode, probs=pr, probs_b=e_pr, q1=q1, q1_b=e1, q2=q2, q2_b=e2)
+    for i, (u, qq, ee) in enumerate(((u1, q1, e1), (u2, q2, e2)), 1):
+        m = (u < qq).double()
+        cnt = float(m.sum())
+        mul = m * (U * C) / cnt if cnt > 0 else torch.zeros_like(m)
+        out["mul%d" % i], out["mul%d_b" % i] = full(mul), torch.cat((torch.zeros_like(ones), U32 * mul.abs()))
+        out["near%d" % i], out["nan%d" % i] = (u - qq).abs() <= ee, cnt == 0
+    return out
+
+
+def channel_drop_check(tag, r, B, mul1, mul2, probs=None):
+    """compares a launch of chap_channel_drop (mul1, mul2 [B + U, C]; probs [U, C] or None) with channel_drop_ref's `r`; returns the worst err / bound.
+    An element whose comparison u < q fp64 cannot decide (`near`; at most NEAR_TIE_CAP of a mask) may take either value: the count is then the kernel's own."""
+    worst = 0.0
+    if probs is not None and r["mode"] == "scores":
+        worst = check(tag + " probs", probs, r["probs"], r["probs_b"], "uc")
+    for i, got in ((1, mul1), (2, mul2)):
+        got = _c(got, r["mul%d" % i])
+        assert bool((got[:B] == 1).all()), (tag, "rows [0, B)")
+        if r["nan%d" % i]:
+            assert bool(torch.isnan(got[B:]).all()), (tag, "an empty mask is 0 / 0 everywhere")
+            continue
+        near = r["near%d" % i]
+        assert float(near.double().mean()) <= NEAR_TIE_CAP, (tag, "near ties", int(near.sum()))
+        ref, bnd = r["mul%d" % i], r["mul%d_b" % i]
+        if bool(near.any()):
+            m = torch.where(near, got[B:] != 0, ref[B:] != 0).double()
+            ref = torch.cat((ref[:B], m * m.numel() / m.sum()))
+            bnd = torch.cat((bnd[:B], U32 * ref[B:]))
+        worst = max(worst, check("%s mul%d" % (tag, i), got, ref, bnd, "nc"))
+    return worst
+
+
+def fold_ref(g, coff, C, mul, B, U, dtype):
+    """chap_fold_perturbed: g [B + U, ..., ld] (values representable in `dtype`), channels [coff, coff + C).  out[n] = g[n] for n < B - U: a copy, exact;
+    out[B - U + u] = fmaf(g[B + u], mul[B + u], g[B - U + u]) (v + w without mul): one fp32 rounding, then the store.  Returns (out [B, ..., C], bound)."""
+    gg = _c(g)[..., coff:coff + C]
+    out = gg[:B].clone()
+    e = torch.zeros_like(out)
+    if U > 0:
+        w = gg[B:]
+        if mul is not None:
+            w = w * _c(mul, gg)[B:].reshape([U] + [1] * (gg.dim() - 2) + [C])
+        out[B - U:] = out[B - U:] + w
+        e[B - U:] = bound(out[B - U:], extra=U32 * out[B - U:].abs(), store=dtype)
+    return out, e
+
+
+def planar_to_cl_ref(x, out0, out_coff=0, cpad=0):
+    """chap_planar_to_cl: fp32 x [N, C, *sp] -> channels [out_coff, out_coff + max(C, cpad)) of out0 [N, ..., ld] (what the buffer held; its dtype is the
+    output's): x rounded to that dtype to nearest even, zeros in [C, cpad), every other element untouched.  Exact: returns the expected tensor."""
+    N, C = x.shape[:2]
+    out = out0.clone()
+    cl = x.reshape(N, C, -1).transpose(1, 2).reshape(*out0.shape[:-1], C)
+    out[..., out_coff:out_coff + C] = cl.to(out0.dtype)
+    if cpad > C:
+        out[..., out_coff + C:out_coff + cpad] = 0
+    return out
+
+
+# chap_cl_to_planar has no restatement of its own: its output IS lazy_f32's (v, dv) -- v within dv, dv = 0 (exact) without an affine -- as [N, C, *sp].
+
+
+# ---- inputs shared by tests/test_eval_plumbing_kernels_gpu.py and tests/test_kernel_ref_cpu.py ------------------------------------------
+ENSEMBLE_SCALES = {"model1": (1.0, 8.0, 30.0), "model2": (1.0, 8.0, 30.0), "logit_ensemble": (1.0, 8.0, 30.0), "prob_ensemble": (1.0, 3.0)}
+
+
+ENSEMBLE_TWO_TRIPS = (3, (419, 419))                        # N, spatial size of the second-grid-stride-trip case (C = 2)
+
+
+def ensemble_inputs(C, scales, N=5, sp=(37, 41), seed=3):
+    """randn logits of two heads times a per-sample scale (cycled over the samples); pixel (0, 0) of sample 0: an exact tie of all classes."""
+    g = torch.Generator().manual_seed(seed)
+    sc = torch.tensor([scales[i % len(scales)] for i in range(N)]).view(N, 1, *([1] * len(sp)))
+    a, b = torch.randn(N, C, *sp, generator=g) * sc, torch.randn(N, C, *sp, generator=g) * sc
+    a[(0, slice(None)) + (0,) * len(sp)] = 1.0
+    b[(0, slice(None)) + (0,) * len(sp)] = 1.0
+    return a, b
+
+
+WINDOW_CASE = dict(vol=(20, 18, 14), patch=(12, 10, 8), calls=(((8, 8, 6), (0, 0, 0), (4, 3, 2)), ((8, 0, 6), (0, 8, 0), (8, 8, 6))))
+
+
+def window_inputs(C, vol, patch, calls, seed=5, scale=4.0):
+    """per call the patch logits (randn * scale); a nonzero prior score / cnt (cnt a small integer), both 0 in the corner block [:2, -2:, -2:] so that an
+    uncovered voxel with nothing in it (0 / 0) exists when no patch reaches that corner."""
+    g = torch.Generator().manual_seed(seed)
+    logits = [torch.randn(len(o), C, *patch, generator=g) * scale for o in calls]
+    score0 = torch.rand(C, *vol, generator=g)
+    cnt0 = torch.randint(1, 4, vol, generator=g).float()
+    score0[:, :2, -2:, -2:] = 0
+    cnt0[:2, -2:, -2:] = 0
+    return logits, score0, cnt0
+
+
+DROP_SHAPES = ((1, 2), (3, 16), (5, 24), (12, 256), (64, 256))
+
+
+def channel_drop_inputs(U, C, nchunk=3, npix=35, seed=0, prob_kind="sigmoid", comp=False, branch=0):
+    """pool_partial [U, nchunk, C] (positive, as sums of activations), grad_sim [C], uniforms u1, u2 [U, C]: drawn, then every u within 4x the bound of its q
+    (channel_drop_ref) is moved to the far side of that band, away from q.  Returns dict(..., moved = their count)."""
+    g = torch.Generator().manual_seed(1000 * U + C + seed)
+    part = torch.rand(U, nchunk, C, generator=g) * npix / nchunk
+    gs = torch.randn(C, generator=g)
+    u1, u2 = torch.rand(U, C, generator=g), torch.rand(U, C, generator=g)
+    r = channel_drop_ref(u1, u2, 0, "scores", pool_partial=part, npix=npix, grad_sim=gs, comp=comp, branch=branch, prob_kind=prob_kind)
+    moved = 0
+    for u, key in ((u1, "q1"), (u2, "q2")):
+        q, e = r[key], 4 * r[key + "_b"]
+        close = (u.double() - q).abs() <= e
+        moved += int(close.sum())
+        away = torch.where(u.double() >= q, q + 2 * e + 1e-6, q - 2 * e - 1e-6).clamp(0.0, 1.0).float()
+        u[close] = away[close]
+    return dict(part=part, gs=gs, u1=u1, u2=u2, npix=npix, moved=moved)

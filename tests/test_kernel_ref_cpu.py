@@ -583,3 +583,371 @@ def test_mutation_p_sgd_tail_not_updated():
     p2, e_p, _, _ = kr.sgd_ref(p, gr, mo, 0.01, 0.9, 1e-4)
     assert fails("mut p", got, p2, e_p)
     assert relerr(got, p2) >= STOL                         # (rejected at lr = 0.01: the step is 1e-2 of a parameter)
+
+
+# ==== evaluation, channel-drop, BatchNorm-finalize and layout kernels ================================================================
+from oracle import filter_dropout as ofd
+from oracle import inference as oinf
+
+
+def test_inference_restatements_equal_torch_and_the_oracle_loop():
+    a, b = kr.ensemble_inputs(4, (1.0, 3.0))
+    ad, bd = a.double(), b.double()
+    want = {"model1": torch.softmax(ad, 1), "model2": torch.softmax(bd, 1), "logit_ensemble": torch.softmax((a + b).double() / 2.0, 1),
+            "prob_ensemble": (torch.softmax(ad, 1) + torch.softmax(bd, 1)) / 2.0}
+    for mode, p in want.items():
+        r = kr.ensemble_ref(a, b, mode)
+        assert close(r["p"], p) and torch.equal(r["label"], p.argmax(1)) and int(r["label"][0, 0, 0]) == 0
+    r = kr.ensemble_ref(a[:, :1], None, "model1")           # C = 1: p = 1, label 0
+    assert bool((r["p"] == 1).all()) and not bool(r["label"].any()) and not bool(r["near"].any())
+    # sliding window: oracle.inference.test_single_case walks the origins x, y, z in {0, 8} x {0, 8} x {0, 6} and calls `net` once per patch
+    C, vol, patch = 3, (20, 18, 14), (12, 10, 8)
+    g = gen(30)
+    origins = [(x, y, z) for x in (0, 8) for y in (0, 8) for z in (0, 6)]
+    logits = torch.randn(len(origins), C, *patch, generator=g, dtype=torch.float64) * 3
+    it = iter(range(len(origins)))
+    label, score = oinf.test_single_case(lambda patch_: logits[next(it)][None], np.zeros(vol, np.float32), 8, 6, patch, num_classes=C)
+    acc = kr.window_accumulate_ref(logits, origins, torch.zeros(C, *vol), torch.zeros(vol))
+    fin = kr.window_finalize_ref(acc["score"], acc["cnt"], acc["score_b"])
+    assert bool(acc["covered"].all()) and not bool(fin["empty"].any())
+    assert np.abs(fin["score"].numpy() - score).max() < 1e-6 and float(acc["cnt"].max()) == 8.0      # (the oracle's score map is fp32)
+    assert np.array_equal(fin["label"].numpy()[~fin["near"].numpy()], label[~fin["near"].numpy()])
+    # an uncovered voxel keeps what it held (bound 0), and 0 / 0 is named
+    lg, s0, c0 = kr.window_inputs(2, **kr.WINDOW_CASE)
+    acc = kr.window_accumulate_ref(lg[0], kr.WINDOW_CASE["calls"][0], s0, c0)
+    unc = ~acc["covered"]
+    assert bool(unc.any()) and torch.equal(acc["score"][:, unc], s0.double()[:, unc]) and float(acc["score_b"][:, unc].max()) == 0.0
+    assert bool(kr.window_finalize_ref(acc["score"], acc["cnt"])["empty"][0, -1, -1])
+
+
+def _bn_case(C=6, nsub=1, nslots=65, N=4, P=130, seed=31, shift=True, count_one=False):
+    """a conv output [N, Clog, P] dealt to `nslots` slots of consecutive pixels; the slot buffer as the convs write it (header, [slot][S | Q][Clog], NaN in the slots
+    not in use) and the same values as a plain tensor [N * P * nsub, C] for F.batch_norm."""
+    g = gen(seed)
+    Clog = C * nsub
+    x = torch.randn(N * P, Clog, generator=g) * 1.5 + torch.randn(Clog, generator=g)
+    if count_one:
+        x = x[:1]
+    sh = (torch.randn(C, generator=g) * 0.5) if shift else None
+    d = x.double() - (sh.double().repeat(nsub) if shift else 0.0)
+    owner = torch.arange(x.shape[0]) % nslots
+    slots = torch.full((max(nslots + 3, 8), 2, Clog), float("nan"))
+    for b in range(nslots):
+        slots[b, 0] = d[owner == b].sum(0).float()
+        slots[b, 1] = (d[owner == b] ** 2).sum(0).float()
+    gam, bet = torch.rand(C, generator=g) + 0.5, torch.randn(C, generator=g) * 0.2
+    rm, rv = torch.randn(C, generator=g) * 0.1, torch.rand(C, generator=g) + 0.5
+    flat = x.reshape(-1, nsub, C).reshape(-1, C)
+    return dict(slots=slots, nslots=nslots, C=C, Clog=Clog, count=flat.shape[0], shift=sh, gam=gam, bet=bet, rm=rm, rv=rv, flat=flat)
+
+
+def _bn_ref(c, momentum=0.125, eps=1e-5):
+    return kr.bn_finalize_ref(c["slots"], c["nslots"], c["C"], c["Clog"], c["count"], c["shift"], c["gam"], c["bet"], c["rm"], c["rv"], momentum, eps)
+
+
+def _bn_emulate(c, momentum=0.125, eps=1e-5, drop_slot=None, clamp_unmasked=False, biased=False):
+    """the kernel's order: fp64 totals over the slots, then fp32."""
+    sl, n = c["slots"][:c["nslots"]].double(), c["nslots"]
+    if drop_slot is not None:
+        sl = torch.cat((sl[:drop_slot], sl[drop_slot + 1:]))
+    tot = sl.sum(0)
+    if clamp_unmasked:
+        tot = tot + (1024 - n) * c["slots"][0].double()
+    S, Q = (t.reshape(-1, c["C"]).sum(0) for t in (tot[0], tot[1]))
+    cnt = float(c["count"])
+    ms = S / cnt
+    var = (Q / cnt - ms * ms).clamp_min(0)
+    f = lambda v: torch.tensor(v, dtype=torch.float32)
+    mean = ((c["shift"].double() if c["shift"] is not None else 0.0) + ms).float()
+    invstd = (1.0 / torch.sqrt(var + float(f(eps)))).float()
+    sc = c["gam"] * invstd
+    out = dict(mean=mean, invstd=invstd, scale=sc, shift=c["bet"] - mean * sc)
+    unb = (var * cnt / (cnt - 1.0) if (cnt > 1 and not biased) else var).float()
+    out["running_mean"] = (1 - f(momentum)) * c["rm"] + f(momentum) * mean
+    out["running_var"] = (1 - f(momentum)) * c["rv"] + f(momentum) * unb
+    return out
+
+
+def _bn_check(name, got, ref, keys=None):
+    for k in keys or ref:
+        kr.check("%s %s" % (name, k), got[k], ref[k][0], ref[k][1], "c")
+
+
+@pytest.mark.parametrize("nsub,nslots,shift", [(1, 1, False), (4, 65, True), (8, 63, True)])
+def test_bn_restatement_equals_batch_norm_fp64(nsub, nslots, shift):
+    c = _bn_case(nsub=nsub, nslots=nslots, shift=shift)
+    r = _bn_ref(c)
+    x = c["flat"].double()
+    rm, rv = c["rm"].double().clone(), c["rv"].double().clone()
+    y = F.batch_norm(x, rm, rv, c["gam"].double(), c["bet"].double(), True, 0.125, 1e-5)
+    # the slot values are fp32 roundings of fp64 partial sums: the totals agree to a few 2^-24 of sum |x|, not to 1e-12
+    tol = lambda v: 1e-5 * max(1.0, float(v.abs().max()))
+    assert (r["mean"][0] - x.mean(0)).abs().max() < tol(x) and (r["running_mean"][0] - rm).abs().max() < tol(rm)
+    assert (r["running_var"][0] - rv).abs().max() < tol(rv)
+    assert (x * r["scale"][0] + r["shift"][0] - y).abs().max() < 1e-4 * float(y.abs().max())
+    assert (r["invstd"][0] - (x.var(0, unbiased=False) + 1e-5).rsqrt()).abs().max() < 1e-5
+    assert "running_mean" not in _bn_ref(c, momentum=0.0)
+    # count = 1: the unbiased variance is the biased one (0), not 0 / 0
+    c1 = _bn_case(count_one=True, nslots=1)
+    r1 = _bn_ref(c1)
+    assert bool(torch.isfinite(r1["running_var"][0]).all()) and float((r1["running_var"][0] - 0.875 * c1["rv"].double()).abs().max()) < 1e-5
+
+
+def test_emulated_correct_bn_finalize_passes_and_faults_c_d_e_fail():
+    for kw in (dict(nsub=1, nslots=65), dict(nsub=4, nslots=63), dict(nsub=8, nslots=1), dict(count_one=True, nslots=1)):
+        c = _bn_case(**kw)
+        _bn_check("bn", _bn_emulate(c), _bn_ref(c))
+    c = _bn_case(nslots=65)
+    ref = _bn_ref(c)
+    got = _bn_emulate(c, drop_slot=64)                      # (c) a lane's second slot (lane 0: slots 0, 64, ...) is lost
+    assert fails("bn mean", got["mean"], *ref["mean"]) and fails("bn scale", got["scale"], *ref["scale"])
+    c = _bn_case(nslots=63)
+    ref = _bn_ref(c)
+    got = _bn_emulate(c, clamp_unmasked=True)               # (d) b < nslots ? b : 0 without the mask: row 0 added for every slot index >= nslots
+    assert fails("bn mean", got["mean"], *ref["mean"]) and fails("bn invstd", got["invstd"], *ref["invstd"])
+    got = _bn_emulate(c, biased=True)                       # (e) count instead of count - 1
+    assert fails("bn running_var", got["running_var"], *ref["running_var"])
+    _bn_check("bn", got, ref, ("mean", "invstd", "scale", "shift", "running_mean"))
+
+
+def test_bn_eval_restatement_and_emulation():
+    g = gen(32)
+    C = 65
+    gam, bet, rm = torch.rand(C, generator=g) + 0.5, torch.randn(C, generator=g), torch.randn(C, generator=g)
+    rv = torch.rand(C, generator=g)
+    rv[0], rv[1] = 0.0, 1e6
+    (sc, e_sc), (sh, e_sh) = kr.bn_eval_ref(gam, bet, rm, rv, 1e-5)
+    x = torch.randn(7, C, generator=g, dtype=torch.float64)
+    y = F.batch_norm(x, rm.double(), rv.double(), gam.double(), bet.double(), False, 0.0, kr._fp32_scalar(1e-5))      # eps as the fp32 scalar the kernel gets
+    assert (x * sc + sh - y).abs().max() < 1e-12 * float(y.abs().max())
+    s32 = gam * torch.rsqrt(rv + 1e-5)
+    kr.check("bn_eval scale", s32, sc, e_sc, "c"), kr.check("bn_eval shift", bet - rm * s32, sh, e_sh, "c")
+    kr.check("bn_eval shift fused", (bet.double() - rm.double() * s32.double()).float(), sh, e_sh, "c")
+    assert fails("bn_eval", gam * torch.rsqrt(rv), sc, e_sc)                  # eps forgotten
+
+
+def _lazy_case(dtype, N=3, C=16, sp=(5, 7), seed=33, lazy=True):
+    g = gen(seed)
+    x = rq(torch.randn(N, C, *sp, generator=g), dtype)
+    kw = {}
+    if lazy:
+        kw = dict(scale=torch.rand(C, generator=g) + 0.5, shift=torch.randn(C, generator=g) * 0.2, act=True, slope=0.01,
+                  keep=(torch.rand(N, C, *sp, generator=g) > 0.3).float(), keep_scale=1.25, chan_mul=(torch.rand(N, C, generator=g) > 0.3).float() * 1.5)
+    return x, kw
+
+
+def _lazy_emulate(x, kw):
+    """src_load8 in fp32 (the affine unfused: within lazy_f32's dv)."""
+    v = x.clone()
+    bc = lambda t: t.view([1, -1] + [1] * (x.dim() - 2))
+    if kw:
+        v = v * bc(kw["scale"]) + bc(kw["shift"])
+        v = torch.where(v > 0, v, v * torch.tensor(kw["slope"], dtype=torch.float32))
+        v = torch.where(kw["keep"] != 0, v * kw["keep_scale"], torch.zeros(()))
+        v = v * kw["chan_mul"].view(list(kw["chan_mul"].shape) + [1] * (x.dim() - 2))
+    return v
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_channel_sums_restatement_emulation_and_fault_f(dtype):
+    x, kw = _lazy_case(dtype, N=3, C=16, sp=(37, 23))
+    lz = kr.lazy_f32(x, **kw)
+    prior = torch.randn(16, generator=gen(34))
+    ref, b = kr.channel_sum_ref(lz, prior)
+    v = _lazy_emulate(x, kw)
+    rows = v.permute(0, 2, 3, 1).reshape(-1, 16)             # pixel-major, 128 pixels per block as C = 16 deals them
+    pad = (-rows.shape[0]) % 128
+    blocks = F.pad(rows, (0, 0, 0, pad)).reshape(-1, 128, 16).flip(1).sum(1)
+    kr.check("channel_sum", prior + blocks.double().sum(0).float(), ref, b, "c")
+    assert fails("channel_sum", prior + blocks[:-1].double().sum(0).float(), ref, b)      # (f) the last, partial block is lost
+    plain = kr.lazy_f32(x)
+    assert close(kr.channel_sum_ref(plain)[0], x.double().sum((0, 2, 3)))
+    r = kr.sample_channel_sum_ref(lz)
+    part = torch.stack([v[:, :, i::7].sum((2, 3)) for i in range(7)], 1)      # rows i, i + 7, ...: one way of dealing the pixels to 7 chunks
+    kr.check("sample sum", part.double().sum(1), r["sum"], r["sum_b"], "nc")
+    kr.check("sample mean", part.double().sum(1) / (37 * 23), r["mean"], r["mean_b"], "nc")
+    assert close(kr.sample_channel_sum_ref(plain)["mean"], x.double().mean((2, 3)))
+
+
+def _drop_emulate(c, B, comp, branch, kind, flip=None):
+    """channel_drop_kernel's score-driven mode in fp32, in its order."""
+    f = lambda v: torch.tensor(v, dtype=torch.float32)
+    U, C = c["u1"].shape
+    a = c["part"][:, 0].clone()
+    for k in range(1, c["part"].shape[1]):
+        a = a + c["part"][:, k]
+    s = c["gs"].view(1, C) * (a * f(1.0 / c["npix"]))
+    mean = s.sum(1, keepdim=True) / C
+    sigma = torch.sqrt(((s - mean) ** 2).sum(1, keepdim=True) / (C - 1))
+    if kind == "gauss":
+        pr = (0.5 * (1 + torch.erf((s - mean) / (sigma * 2.0 + f(1e-8)) * f(0.70710678118654752)))).clamp(0, 1)
+    else:
+        pr = 1.0 / (1.0 + torch.exp(2.0 * ((s - mean) / (sigma + f(1e-8)))))
+    pk = 1.0 - pr
+    m1 = (c["u1"] < (pr if comp and branch == 1 else pk)).float()
+    m2 = (c["u2"] < (pr if comp and branch == 0 else pk)).float()
+    if flip is not None:
+        m1[flip] = 1.0 - m1[flip]
+    ones = torch.ones(B, C)
+    return pr, torch.cat((ones, m1 * (U * C) / m1.sum())), torch.cat((ones, m2 * (U * C) / m2.sum()))
+
+
+@pytest.mark.parametrize("kind", ["sigmoid", "gauss"])
+def test_channel_drop_restatement_emulation_and_fault_g(kind):
+    for (U, C), (comp, branch) in zip(kr.DROP_SHAPES[1:4], ((False, 0), (True, 0), (True, 1))):
+        c = kr.channel_drop_inputs(U, C, prob_kind=kind, comp=comp, branch=branch)
+        B = 2 * U
+        r = kr.channel_drop_ref(c["u1"], c["u2"], B, "scores", pool_partial=c["part"], npix=c["npix"], grad_sim=c["gs"], comp=comp, branch=branch, prob_kind=kind)
+        # the oracle in fp64 (its activation: the pooled mean; its 1e-8 and 1 / npix are doubles: agreement to 1e-7, not 1e-12)
+        act = c["part"].double().sum(1) / c["npix"]
+        want = ofd.drop_probs(c["gs"].double(), act, kind)
+        assert (r["probs"] - want).abs().max() < 1e-6
+        m1, m2 = ofd.drop_based_on_prob(want, comp, c["u1"].double(), c["u2"].double(), branch)
+        assert (r["mul1"][B:] - m1[..., 0, 0]).abs().max() < 1e-6 * U * C and (r["mul2"][B:] - m2[..., 0, 0]).abs().max() < 1e-6 * U * C      # (the oracle's masks are fp32)
+        assert not bool(r["near1"].any()) and not bool(r["near2"].any())      # the GPU test's near-tie share on these seeds: 0
+        pr, e1, e2 = _drop_emulate(c, B, comp, branch, kind)
+        kr.check("probs", pr, r["probs"], r["probs_b"], "uc"), kr.check("mul1", e1, r["mul1"], r["mul1_b"], "nc"), kr.check("mul2", e2, r["mul2"], r["mul2_b"], "nc")
+        # (g) one flipped comparison moves every kept element of that mask by 1 / count: each of them fails on its own
+        _, bad, _ = _drop_emulate(c, B, comp, branch, kind, flip=(U - 1, C - 1))
+        wrong = (bad.double() - r["mul1"]).abs() > r["mul1_b"]
+        assert int(wrong.sum()) == int(((r["mul1"][B:] != 0) | (bad[B:] != 0)).sum()) and not bool(wrong[:B].any())
+    # modes 0 / 1 and the all-zero fallback
+    c = kr.channel_drop_inputs(3, 16)
+    r0 = kr.channel_drop_ref(c["u1"], c["u2"], 3, "dropout2d")
+    rz = kr.channel_drop_ref(c["u1"], c["u2"], 3, "scores", pool_partial=c["part"], npix=c["npix"], grad_sim=torch.zeros(16))
+    assert rz["mode"] == "dropout2d" and torch.equal(r0["mul1"], rz["mul1"]) and torch.equal(r0["mul2"], rz["mul2"])
+    assert torch.equal(r0["mul1"][3:], (c["u1"] < 0.5).double() * 2) and bool((r0["mul1"][:3] == 1).all())
+    r1 = kr.channel_drop_ref(c["u1"], c["u2"], 3, "comp_binomial")
+    assert torch.equal(r1["mul1"][3:] + r1["mul2"][3:], torch.full((3, 16), 2.0, dtype=torch.float64))
+    # an empty mask is named, as 0 / 0 is NaN in the definition
+    re = kr.channel_drop_ref(torch.ones(3, 16), c["u2"], 3, "scores", pool_partial=c["part"], npix=c["npix"], grad_sim=c["gs"])
+    assert re["nan1"] and not re["nan2"]
+    with np.errstate(invalid="ignore"):
+        assert bool(torch.isnan(ofd.drop_based_on_prob(re["probs"], False, torch.ones(3, 16).double(), c["u2"].double())[0]).all())
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_fold_restatement_equals_autograd_emulation_and_fault_h(dtype):
+    g = gen(35)
+    B, U, C, ld, coff = 4, 2, 16, 32, 8
+    gfull = rq(torch.randn(B + U, 3, 5, ld, generator=g), dtype)
+    mul = torch.cat((torch.ones(B, C), (torch.rand(U, C, generator=g) > 0.4).float() * 1.7))
+    ref, b = kr.fold_ref(gfull, coff, C, mul, B, U, dtype)
+    f = torch.zeros(B, C, 3, 5, dtype=torch.float64, requires_grad=True)
+    cot = gfull[..., coff:coff + C].permute(0, 3, 1, 2).double()
+    (torch.cat((f, mul[B:].double().view(U, C, 1, 1) * f[B - U:])) * cot).sum().backward()
+    assert close(ref, f.grad.permute(0, 2, 3, 1))
+    gs = gfull[..., coff:coff + C]
+    emu = gs[:B].clone()
+    emu[B - U:] = (emu[B - U:].double() + gs[B:].double() * mul[B:].double().view(U, 1, 1, C)).float()      # the kernel's fmaf: one rounding
+    kr.check("fold", emu.to(dtype), ref, b, "nhwc")
+    assert float(b[:B - U].max()) == 0.0
+    bad = gs[:B].clone()
+    bad[B - U:] += gs[B:] * mul[B - 1:B + U - 1].view(U, 1, 1, C)           # (h) mul of sample u - 1
+    assert fails("fold", bad.to(dtype), ref, b)
+    ref0, b0 = kr.fold_ref(gfull, coff, C, None, B, 0, dtype)
+    assert torch.equal(ref0, gs[:B].double()) and float(b0.max()) == 0.0
+
+
+def test_layout_restatements_and_fault_i():
+    g = gen(36)
+    x = torch.randn(2, 3, 4, 5, generator=g)
+    x[0, 0, 0, :4] = torch.tensor([1.00390625, 1.01171875, -1.00390625, 1.0 + 2.0 ** -8 + 2.0 ** -20])     # bf16 ties (to even: 1.0, 1.015625, -1.0) and just above one
+    out0 = torch.full((2, 1, 4, 5, 32), float("nan"), dtype=torch.bfloat16)
+    ref = kr.planar_to_cl_ref(x, out0, out_coff=8, cpad=8)
+    assert ref[0, 0, 0, :4, 8].tolist() == [1.0, 1.015625, -1.0, 1.0078125]
+    assert torch.equal(ref[..., 8:11].float(), x.permute(0, 2, 3, 1).unsqueeze(1).bfloat16().float()) and bool((ref[..., 11:16] == 0).all())
+    assert bool(torch.isnan(ref[..., :8]).all()) and bool(torch.isnan(ref[..., 16:]).all())
+    def emulate(width):
+        """planar_to_cl8_kernel's walk: per (sample, pixel) `width` channels from out_coff on, the first C converted, the rest zero."""
+        o = out0.clone().reshape(2, 20, 32)
+        xf = x.reshape(2, 3, 20)
+        for n in range(2):
+            for pp in range(20):
+                for c in range(width):
+                    o[n, pp, 8 + c] = xf[n, c, pp].bfloat16() if c < 3 else 0.0
+        return o.reshape(out0.shape)
+    bits = lambda t: t.view(torch.int16)
+    assert torch.equal(bits(emulate(8)), bits(ref))
+    bad = bits(emulate(9)) != bits(ref)                     # (i) the zero pad written one channel too far: every pixel's channel 16, nothing else
+    assert int(bad.sum()) == 2 * 20 and bool(bad[..., 16].all())
+    for C, ld, coff, cpad in ((1, 1, 0, 0), (3, 12, 4, 5)):  # no pad; a pad and a slice the vector path cannot take
+        o0 = torch.full((2, 1, 4, 5, ld), float("nan"))
+        r = kr.planar_to_cl_ref(x[:, :C], o0, coff, cpad)
+        w = max(C, cpad)
+        want = F.pad(x[:, :C].permute(0, 2, 3, 1).unsqueeze(1), (0, w - C))
+        assert torch.equal(r[..., coff:coff + w], want) and int(torch.isnan(r).sum()) == 40 * (ld - w)
+    v, dv = kr.lazy_f32(x)                                  # cl_to_planar of a plain source: the values themselves, exactly
+    assert torch.equal(v, x.double()) and float(dv.max()) == 0.0
+
+
+# ---- emulated inference kernels, faults (a) and (b), and the near-tie shares of the GPU inputs -------------------------------------
+def _emulate_window(logits, origins, score0, cnt0, skip=None):
+    s, c = score0.clone(), cnt0.clone()
+    pw, ph, pd = logits.shape[2:]
+    sm = torch.softmax(logits, 1)
+    for k, (x, y, z) in enumerate(origins):
+        s[:, x:x + pw, y:y + ph, z:z + pd] += sm[k]
+        c[x:x + pw, y:y + ph, z:z + pd] += 1
+    if skip is not None:
+        k, (x, y, z) = skip
+        ox, oy, oz = origins[k]
+        s[:, x, y, z] -= sm[k][:, x - ox, y - oy, z - oz]
+    return s, c
+
+
+def test_emulated_inference_kernels_pass_and_faults_a_b_fail():
+    for C in (1, 2, 4, 8):
+        for mode in kr.ENSEMBLE_SCALES:
+            a, b = kr.ensemble_inputs(C, (1.0, 8.0, 30.0))
+            r = kr.ensemble_ref(a, b, mode)
+            emu = {"model1": torch.softmax(a, 1), "model2": torch.softmax(b, 1), "logit_ensemble": torch.softmax((a + b) / 2.0, 1),
+                   "prob_ensemble": (torch.softmax(a, 1) + torch.softmax(b, 1)) / 2.0}[mode]
+            kr.check("ensemble " + mode, emu, r["p"], r["e_p"])
+            ok = ~r["near"]
+            assert torch.equal(emu.argmax(1)[ok], r["label"][ok])
+    lg, s0, c0 = kr.window_inputs(8, **kr.WINDOW_CASE)
+    calls = kr.WINDOW_CASE["calls"]
+    acc = kr.window_accumulate_ref(lg[0], calls[0], s0, c0)
+    s, c = _emulate_window(lg[0], calls[0], s0, c0)
+    kr.check("window score", s, acc["score"], acc["score_b"], "cxyz")
+    assert torch.equal(c.double(), acc["cnt"]) and torch.equal(s[:, ~acc["covered"]], s0[:, ~acc["covered"]])
+    bad, _ = _emulate_window(lg[0], calls[0], s0, c0, skip=(2, (10, 8, 5)))     # (a) the last patch of the batch missing from one voxel
+    assert fails("window score", bad, acc["score"], acc["score_b"])
+    assert np.allclose(bad.numpy(), acc["score"].numpy(), atol=1.0) and not np.allclose(bad.numpy(), acc["score"].numpy(), atol=1e-6)
+    fin = kr.window_finalize_ref(s, c)
+    live = ~fin["empty"]
+    q = torch.where(live, s / c, torch.zeros(()))
+    kr.check("window fin", q, fin["score"], fin["score_b"], "cxyz")
+    qb = torch.where(live, s / c.roll(1, 2), torch.zeros(()))                  # (b) the count of the neighbouring voxel
+    assert fails("window fin", torch.where(torch.isfinite(qb), qb, torch.zeros(())), fin["score"], fin["score_b"])
+
+
+def test_near_tie_shares_of_the_inference_inputs():
+    """the conditions of tests/test_eval_plumbing_kernels_gpu.py, from the reference alone: the share of pixels left out of the label comparison."""
+    for C in (2, 4, 8):
+        for mode, scales in kr.ENSEMBLE_SCALES.items():
+            r = kr.ensemble_ref(*kr.ensemble_inputs(C, scales), mode)
+            assert float(r["near"].double().mean()) <= kr.NEAR_TIE_CAP and int(r["near"].sum()) == 0, (C, mode)
+            top = r["p"].topk(2, dim=1).values
+            assert bool(top[0, 0, 0, 0] == top[0, 1, 0, 0])                   # the exact tie stays in the comparison
+    N, sp = kr.ENSEMBLE_TWO_TRIPS                           # the second-grid-stride-trip inputs, whose labels the GPU test compares as well
+    for mode, scales in kr.ENSEMBLE_SCALES.items():
+        r = kr.ensemble_ref(*kr.ensemble_inputs(2, scales, N=N, sp=sp), mode)
+        assert float(r["near"].double().mean()) <= kr.NEAR_TIE_CAP, (mode, int(r["near"].sum()))
+    # what scales (1, 8, 30) do to prob_ensemble: two saturated heads that disagree put two classes at 0.5 +- one ulp
+    r = kr.ensemble_ref(*kr.ensemble_inputs(4, (1.0, 8.0, 30.0)), "prob_ensemble")
+    assert float(r["near"].double().mean()) > 0.01
+    for C in (2, 8):
+        lg, s0, c0 = kr.window_inputs(C, **kr.WINDOW_CASE)
+        s, c = s0.double(), c0.double()
+        for l, o in zip(lg, kr.WINDOW_CASE["calls"]):
+            acc = kr.window_accumulate_ref(l, o, s, c)
+            s, c = acc["score"], acc["cnt"]
+        fin = kr.window_finalize_ref(s, c)
+        assert float(fin["near"].double().mean()) <= kr.NEAR_TIE_CAP and bool(fin["empty"].any()) and not bool(acc["covered"].all())
+    for kind in ("sigmoid", "gauss"):
+        for U, C in kr.DROP_SHAPES:
+            c = kr.channel_drop_inputs(U, C, prob_kind=kind)
+            r = kr.channel_drop_ref(c["u1"], c["u2"], U, "scores", pool_partial=c["part"], npix=c["npix"], grad_sim=c["gs"], prob_kind=kind)
+            assert int(r["near1"].sum()) + int(r["near2"].sum()) == 0 and c["moved"] <= 1 + U * C // 1000

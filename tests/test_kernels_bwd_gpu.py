@@ -147,8 +147,14 @@ def test_act_bn_backward_with_pool(dtype):
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("dims", [2, 3])
 def test_first_conv_backward(dtype, dims):
+    """then 269 120 pixels, just above 1024 blocks * 256 -- the second grid-stride trip every real batch takes -- with dW / db accumulated (+=) onto a nonzero prior."""
+    _first_conv_backward(dtype, dims, (2, 1, 20, 28) if dims == 2 else (1, 6, 10, 12), False)
+    _first_conv_backward(dtype, dims, (5, 1, 232, 232) if dims == 2 else (1, 40, 58, 116), True)
+
+
+def _first_conv_backward(dtype, dims, shape, prior):
     g = torch.Generator().manual_seed(14)
-    shape = (2, 1, 20, 28) if dims == 2 else (1, 6, 10, 12)
+    assert (shape[0] * shape[1] * shape[2] * shape[3] > 1024 * 256) == prior
     x = torch.randn(shape, generator=g)
     w = (torch.randn(16, 1, *([3] * dims), generator=g) / 3).requires_grad_(True)
     b = torch.zeros(16, requires_grad=True)
@@ -158,17 +164,21 @@ def test_first_conv_backward(dtype, dims):
     y.backward(gy)
     gd = cl(gy, dtype)
     dx = torch.empty(shape, device=DEV)
-    dw = torch.zeros_like(w, device=DEV); db = torch.zeros(16, device=DEV)
+    pw = torch.randn(w.shape, generator=g) * 30 if prior else torch.zeros(w.shape)
+    pb = torch.randn(16, generator=g) * 30 if prior else torch.zeros(16)
+    dw = pw.to(DEV); db = pb.to(DEV)
     ops.conv_c1_bwd(gd, w.detach().to(DEV), x.to(DEV), dims=dims, dx=dx, dw=dw, db=db)
     tol = 1e-4 if dtype == torch.float32 else 1e-2
     assert relerr(dx, xin.grad.reshape(shape)) < tol
-    assert relerr(dw, w.grad) < tol and relerr(db, b.grad) < tol
+    assert relerr(dw.cpu() - pw, w.grad) < tol and relerr(db.cpu() - pb, b.grad) < tol
     from tests import kernel_ref as kr
     gyd = gy.double()
     rw = kr.wgrad_ref(xin.detach().double(), gyd, ksize=3, stride=1)
     taps = 3 ** dims
-    kr.check("c1 dW", dw, kr.to_layout(rw["dw"], (1, taps, taps), w.shape), kr.to_layout(kr.wgrad_bound(rw), (1, taps, taps), w.shape))
-    kr.check("c1 db", db, rw["db"], kr.wgrad_bound(rw, which="db"))
+    st = (1, taps, taps)
+    pw3 = pw.double().as_strided((taps, 1, 16), st) if prior else None
+    kr.check("c1 dW", dw, kr.to_layout(rw["dw"], st, w.shape) + pw.double(), kr.to_layout(kr.wgrad_bound(rw, pw3), st, w.shape))
+    kr.check("c1 db", db, rw["db"] + pb.double(), kr.wgrad_bound(rw, pb if prior else None, which="db"))
     r = kr.conv_ref(kr.PACK_CONV_DGRAD, gyd, w.detach().double())
     kr.check("c1 dx", dx.reshape(r["y"].shape), r["y"], kr.conv_bound(r, torch.float32))
 

@@ -5,7 +5,9 @@ CHAP_GROUP=0): the stream schedule, grouping and graph replay are asserted bit-i
 eager == replay tests).  One warm-up step, then one instrumented step: on the FIRST call of each signature (op, shapes, flags,
 dtype) the wrapper synchronises, snapshots what the call accumulates into, launches, synchronises, and checks every output element
 against the fp64 restatement with the per-element bound.  The loss, VAT / BCP, RNG, mask and optimizer launches are checked the same way
-(exactly where the result is a label, a mask or a draw; largest_cc through scipy on the host).  Run with -s for one line per signature
+(exactly where the result is a label, a mask or a draw; largest_cc through scipy on the host), and so are bn_finalize (from the slots the conv
+just wrote, with the running statistics snapshotted), the first conv's backward, the channel sums, the layout copies and the channel-drop kernels:
+no entry point a step calls is left without a restatement.  Run with -s for one line per signature
 (worst err / bound; 0.000 for an exact comparison)."""
 import random
 
@@ -25,17 +27,8 @@ from tests import kernel_ref as kr
 
 DEV = torch.device("cuda", 0)
 
-# ops.* entry points called during a step that are not restated here, and the test covering each
-EXCLUDED = {
-    "bn_finalize": "tests/test_kernels_gpu.py::test_pool_upsample_bnfinalize / test_conv3d_family (running statistics, sub-lattice rows)",
-    "conv_c1_bwd": "tests/test_kernels_bwd_gpu.py::test_first_conv_backward",
-    "channel_sum": "the deconv bias gradient; tests/test_net2d_gpu.py / test_train_step_gpu.py gradients",
-    "bn_eval_affine": "tests/test_kernels_gpu.py::test_pool_upsample_bnfinalize (eval-mode affine)",
-    "planar_to_cl": "layout copy; tests/test_kernels_gpu.py::test_first_conv_direct_equals_padded_path",
-    "cl_to_planar": "layout copy; tests/test_net2d_gpu.py / test_net3d_gpu.py logits",
-    "sample_channel_sum": "tests/test_filter_dropout_gpu.py", "channel_drop": "tests/test_filter_dropout_gpu.py",
-    "fold_perturbed": "tests/test_iteration_conditioning_gpu.py / test_training_parity_gpu.py",
-}
+# ops.* entry points a step may call without a restatement below: none (an entry needs a sentence saying why its full-size fp64 restatement is not affordable)
+EXCLUDED = {}
 HELPERS = {"dt", "pack_weights", "stats_size", "stats_buffer", "stats_totals", "stats_from_moments", "act_bwd_sums_size"}
 
 
@@ -385,6 +378,93 @@ class Checker:
         f(*a, **k)
         torch.cuda.synchronize()
         return [kr.check("grad_sim", q["score"], ref, b, "c")]
+
+    # ---- BatchNorm finalize / eval affine, the first conv's backward, channel sums, layout copies, the channel-drop kernels
+    def bn_finalize(self, f, stats, gamma, beta, running_mean, running_var, nbt, count, eps, momentum, scale, shift, mean=None, invstd=None,
+                    stats_shift=None, clog=None):
+        C = gamma.numel()
+        clog = C if clog is None else clog
+        nslots = int(stats[:1].view(torch.int32).item())
+        slots = stats[_lib.STATS_HDR:_lib.STATS_HDR + nslots * 2 * clog].view(nslots, 2, clog).clone()
+        snap = lambda t: None if t is None else t.clone()
+        rm0, rv0, sh0, nbt0 = snap(running_mean), snap(running_var), snap(stats_shift), snap(nbt)      # stats_shift may BE running_mean
+        f(stats, gamma, beta, running_mean, running_var, nbt, count, eps, momentum, scale, shift, mean=mean, invstd=invstd, stats_shift=stats_shift, clog=clog)
+        torch.cuda.synchronize()
+        ref = kr.bn_finalize_ref(slots, nslots, C, clog, count, sh0, gamma, beta, rm0, rv0, momentum, eps)
+        outs = dict(scale=scale, shift=shift, mean=mean, invstd=invstd, running_mean=running_mean, running_var=running_var)
+        worst = [kr.check("bn_finalize " + k, outs[k], ref[k][0], ref[k][1], "c") for k in ref if outs[k] is not None]
+        if "running_mean" in ref:
+            assert nbt is None or int(nbt) == int(nbt0) + 1
+        elif running_mean is not None:
+            assert torch.equal(running_mean, rm0) and torch.equal(running_var, rv0) and (nbt is None or int(nbt) == int(nbt0))
+        return worst
+
+    def bn_eval_affine(self, f, gamma, beta, running_mean, running_var, eps, scale, shift):
+        f(gamma, beta, running_mean, running_var, eps, scale, shift)
+        torch.cuda.synchronize()
+        (sc, e_sc), (sh, e_sh) = kr.bn_eval_ref(gamma, beta, running_mean, running_var, eps)
+        return [kr.check("bn_eval scale", scale, sc, e_sc, "c"), kr.check("bn_eval shift", shift, sh, e_sh, "c")]
+
+    def conv_c1_bwd(self, f, g, w, x, *, dims, dx=None, dw=None, db=None):
+        p_dw, p_db = (None if t is None else t.detach().double().clone() for t in (dw, db))
+        f(g, w, x, dims=dims, dx=dx, dw=dw, db=db)
+        torch.cuda.synchronize()
+        gy = nc(g, dims).double()
+        worst = []
+        if dw is not None or db is not None:
+            A = x.double().reshape(gy.shape[0], 1, *gy.shape[2:])
+            rw = kr.wgrad_ref(A, gy, ksize=3, stride=1)
+            taps = 3 ** dims
+            st = (1, taps, taps)
+            if dw is not None:
+                worst.append(kr.check("conv_c1_bwd dW", dw, kr.to_layout(rw["dw"], st, dw.shape) + p_dw,
+                                      kr.to_layout(kr.wgrad_bound(rw, p_dw.as_strided((taps, 1, dw.shape[0]), st)), st, dw.shape)))
+            if db is not None:
+                worst.append(kr.check("conv_c1_bwd db", db, rw["db"] + p_db, kr.wgrad_bound(rw, p_db, which="db"), "c"))
+        if dx is not None:
+            r = kr.conv_ref(kr.PACK_CONV_DGRAD, gy, w.detach().double())
+            worst.append(kr.check("conv_c1_bwd dx", dx.reshape(r["y"].shape), r["y"], kr.conv_bound(r, torch.float32)))
+        return worst
+
+    def channel_sum(self, f, lazy, out):
+        prior = out.clone()
+        f(lazy, out)
+        torch.cuda.synchronize()
+        ref, b = kr.channel_sum_ref(lazy_nc(lazy, 3), prior)
+        return [kr.check("channel_sum", out, ref, b, "c")]
+
+    def planar_to_cl(self, f, x, out, out_coff=0, cpad=0):
+        out0 = out.clone()
+        f(x, out, out_coff=out_coff, cpad=cpad)
+        torch.cuda.synchronize()
+        iv = torch.int32 if out.dtype == torch.float32 else torch.int16
+        assert torch.equal(out.view(iv), kr.planar_to_cl_ref(x, out0, out_coff, cpad).view(iv)), "planar_to_cl"
+        return [0.0]
+
+    def cl_to_planar(self, f, lazy, out):
+        f(lazy, out)
+        torch.cuda.synchronize()
+        v, dv = lazy_nc(lazy, 3)                            # the output is the lazy value itself (exact without an affine)
+        return [kr.check("cl_to_planar", out.reshape(v.shape), v, dv)]
+
+    def sample_channel_sum(self, f, lazy, nchunk=32):
+        f(lazy, nchunk=nchunk)
+        torch.cuda.synchronize()
+        r = kr.sample_channel_sum_ref(lazy_nc(lazy, 3))
+        tot = self._last(f).double().sum(1)
+        return [kr.check("sample_channel_sum", tot, r["sum"], r["sum_b"], "nc"), kr.check("sample_channel_sum mean", tot / lazy.raw[0, ..., 0].numel(), r["mean"], r["mean_b"], "nc")]
+
+    def channel_drop(self, f, mul1, mul2, u1, u2, B, mode, **k):
+        f(mul1, mul2, u1, u2, B, mode, **k)
+        torch.cuda.synchronize()
+        r = kr.channel_drop_ref(u1, u2, B, mode, **{n: v for n, v in k.items() if n != "probs_out"})
+        return [kr.channel_drop_check("channel_drop", r, B, mul1, mul2, k.get("probs_out"))]
+
+    def fold_perturbed(self, f, g, coff, Cc, mul, B, U):
+        f(g, coff, Cc, mul, B, U)
+        torch.cuda.synchronize()
+        ref, b = kr.fold_ref(g, coff, Cc, mul, B, U, g.dtype)
+        return [kr.check("fold_perturbed", self._last(f), ref, b, "ndhwc")]
 
     @staticmethod
     def _last(f):
