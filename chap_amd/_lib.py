@@ -114,6 +114,10 @@ class MixLossParams(C.Structure):
                 ("N", _i32), ("C", _i32), ("P", _i32), ("smooth", _f32), ("k_dice", _f32), ("k_ce", _f32), ("gscale_dev", _vp)]
 
 
+class MixLossMultiParams(C.Structure):
+    _fields_ = [("nterms", _i32), ("term", MixLossParams * 4)]
+
+
 class PseudoParams(C.Structure):
     _fields_ = [("logits1", _vp), ("logits2", _vp), ("soft1", _vp), ("soft2", _vp), ("arg1", _vp), ("arg2", _vp),
                 ("knowledge", _vp), ("N", _i32), ("C", _i32), ("P", _i32)]
@@ -178,6 +182,10 @@ class BoxMixParams(C.Structure):
 
 class BoxMaskParams(C.Structure):
     _fields_ = [("mask", _vp), ("box", _vp), ("N", _i32), ("H", _i32), ("W", _i32), ("D", _i32)]
+
+
+class BcpMixParams(C.Structure):
+    _fields_ = [("a", _vp * 2), ("b", _vp * 2), ("out", _vp * 2), ("mask", _vp), ("box", _vp), ("N", _i32 * 2), ("Nm", _i32), ("H", _i32), ("W", _i32), ("D", _i32)]
 
 
 class LccParams(C.Structure):
@@ -249,6 +257,7 @@ _SIGS = {  # name -> (restype, params struct or None)
     "chap_sample_channel_sum": SampleChanSumParams, "chap_channel_drop": ChannelDropParams,
     "chap_fold_perturbed": FoldParams, "chap_grad_sim": GradSimParams, "chap_metrics": MetricsParams,
     "chap_augment2d": Augment2dParams, "chap_augment3d": Augment3dParams,
+    "chap_mix_loss_multi_fwd": MixLossMultiParams, "chap_mix_loss_multi_bwd": MixLossMultiParams, "chap_bcp_mix": BcpMixParams,
 }
 _SIZE_FNS = {"chap_pack_size": PackParams, "chap_conv_c1_bwd_ws": ConvC1BwdParams, "chap_wgrad_ws": WgradParams,
              "chap_lcc_ws": LccParams, "chap_metrics_ws": MetricsParams}

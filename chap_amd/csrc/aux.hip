@@ -151,6 +151,32 @@ extern "C" int chap_box_mask(const chap_boxmask_params* p, void* stream) {
     CHAP_LAUNCH_CHECK("chap_box_mask");
     return CHAP_OK;
 }
+// loss_mask and both halves of the mixed input from one grid: elements [0, n0) are half 0, [n0, n0 + n1) half 1, the rest the mask.
+__global__ void bcpmix_kernel(const chap_bcpmix_params P, int D) {
+    const long vol = (long)D * P.H * P.W, n0 = P.N[0] * vol, n1 = n0 + P.N[1] * vol, total = n1 + P.Nm * vol;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int part = i < n0 ? 0 : i < n1 ? 1 : 2;
+        const long j = i - (part == 0 ? 0 : part == 1 ? n0 : n1);
+        const unsigned uj = (unsigned)j;
+        const int x = (int)(uj % (unsigned)P.W), y = (int)((uj / (unsigned)P.W) % (unsigned)P.H), z = (int)((uj / (unsigned)(P.W * P.H)) % (unsigned)D);
+        const bool in = in_box(P.box, D, z, y, x);
+        if (part == 2) P.mask[j] = in ? 0 : 1;
+        else (part ? P.out[1] : P.out[0])[j] = in ? (part ? P.b[1] : P.b[0])[j] : (part ? P.a[1] : P.a[0])[j];
+    }
+}
+extern "C" int chap_bcp_mix(const chap_bcpmix_params* p, void* stream) {
+    CHAP_CHECK_ARG(p && p->a[0] && p->b[0] && p->out[0] && p->a[1] && p->b[1] && p->out[1] && p->mask && p->box, "chap_bcp_mix: null argument");
+    CHAP_CHECK_ARG(p->N[0] > 0 && p->N[1] > 0 && p->Nm > 0 && p->H > 0 && p->W > 0, "chap_bcp_mix: empty argument");
+    const int D = p->D > 1 ? p->D : 1;
+    const long vol = (long)D * p->H * p->W;
+    const long most = (long)(p->N[0] > p->N[1] ? (p->N[0] > p->Nm ? p->N[0] : p->Nm) : (p->N[1] > p->Nm ? p->N[1] : p->Nm)) * vol;
+    CHAP_CHECK_ARG(most < (1L << 32), "chap_bcp_mix: %ld elements in one part exceed the 32-bit element index", most);
+    const long total = ((long)p->N[0] + p->N[1] + p->Nm) * vol;
+    const int nb = chap_blocks(total, 2048);
+    hipLaunchKernelGGL(bcpmix_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, *p, D);
+    CHAP_LAUNCH_CHECK("chap_bcp_mix");
+    return CHAP_OK;
+}
 
 // ---- spatial perturbation mask: avg-pool(scale) -> per-sample k-th largest -> mask --------------
 __global__ void diffmask_pool_kernel(const chap_diffmask_params P) {

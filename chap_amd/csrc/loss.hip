@@ -64,8 +64,9 @@ __device__ __forceinline__ void softmax_px(const float* __restrict__ lg, long ba
 }
 
 // acc layout per part k in {a, b}: [0] ce_sum, [1..C] I_c, [1+C..2C] Z_c, [1+2C..3C] Y_c, [1+3C] msum
+// `blk` of `nblk`: this block's index within its term and the term's block count (the single-term kernel: blockIdx.x of gridDim.x).
 template <int C>
-__global__ __launch_bounds__(256) void mix_loss_acc_kernel(const chap_mix_loss_params P_) {
+__device__ __forceinline__ void mix_loss_acc_body(const chap_mix_loss_params& P_, const int blk, const int nblk) {
     constexpr int NA = 2 + 3 * C;
     __shared__ float red[4][2 * NA];
     float a[2][NA];
@@ -74,7 +75,7 @@ __global__ __launch_bounds__(256) void mix_loss_acc_kernel(const chap_mix_loss_p
 #pragma unroll
         for (int i = 0; i < NA; ++i) a[k][i] = 0.f;
     const long P = P_.P, total = (long)P_.N * P;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    for (long i = (long)blk * 256 + threadIdx.x; i < total; i += (long)nblk * 256) {
         const long n = (unsigned)i / (unsigned)P, pp = (unsigned)i % (unsigned)P;
         float z[C], p[C], lse;
         softmax_px<C>(P_.logits, n * C * P + pp, P, z, p, lse);
@@ -105,11 +106,13 @@ __global__ __launch_bounds__(256) void mix_loss_acc_kernel(const chap_mix_loss_p
         }
     __syncthreads();
     // this block's partial row (fixed order over the four waves; no atomics): acc[1 + block][2*NA]
-    for (int i = threadIdx.x; i < 2 * NA; i += 256) P_.acc[(long)(1 + blockIdx.x) * 2 * NA + i] = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
+    for (int i = threadIdx.x; i < 2 * NA; i += 256) P_.acc[(long)(1 + blk) * 2 * NA + i] = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
 }
+template <int C>
+__global__ __launch_bounds__(256) void mix_loss_acc_kernel(const chap_mix_loss_params P_) { mix_loss_acc_body<C>(P_, blockIdx.x, gridDim.x); }
 
 // Totals (row 0 of acc, fixed-order sum of the block partials) and the mix_loss return triple (train_ours_2D.py:205-216).
-__global__ __launch_bounds__(256) void mix_loss_final_kernel(float* acc, int nblocks, float* loss, int C, float w_a, float w_b, float smooth, float k_dice, float k_ce) {
+__device__ __forceinline__ void mix_loss_final_body(float* acc, int nblocks, float* loss, int C, float w_a, float w_b, float smooth, float k_dice, float k_ce) {
     __shared__ float tot[2 * (2 + 3 * 8)];
     const int NA = 2 + 3 * C;
     sum_partial_rows(acc, nblocks, 2 * NA, tot);
@@ -126,9 +129,12 @@ __global__ __launch_bounds__(256) void mix_loss_final_kernel(float* acc, int nbl
     }
     loss[0] = part[0]; loss[1] = part[1]; loss[2] = part[0] + part[1];
 }
+__global__ __launch_bounds__(256) void mix_loss_final_kernel(float* acc, int nblocks, float* loss, int C, float w_a, float w_b, float smooth, float k_dice, float k_ce) {
+    mix_loss_final_body(acc, nblocks, loss, C, w_a, w_b, smooth, k_dice, k_ce);
+}
 
 template <int C>
-__global__ __launch_bounds__(256) void mix_loss_bwd_kernel(const chap_mix_loss_params P_) {
+__device__ __forceinline__ void mix_loss_bwd_body(const chap_mix_loss_params& P_, const int blk, const int nblk) {
     constexpr int NA = 2 + 3 * C;
     __shared__ float sa[2 * NA];
     for (int i = threadIdx.x; i < 2 * NA; i += 256) sa[i] = P_.acc[i];
@@ -136,7 +142,7 @@ __global__ __launch_bounds__(256) void mix_loss_bwd_kernel(const chap_mix_loss_p
     const long P = P_.P, total = (long)P_.N * P;
     const float w[2] = {P_.w_a, P_.w_b};
     const float gsc = P_.gscale * (P_.gscale_dev ? *P_.gscale_dev : 1.f);
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    for (long i = (long)blk * 256 + threadIdx.x; i < total; i += (long)nblk * 256) {
         const long n = (unsigned)i / (unsigned)P, pp = (unsigned)i % (unsigned)P;
         float z[C], p[C], lse;
         softmax_px<C>(P_.logits, n * C * P + pp, P, z, p, lse);
@@ -171,9 +177,35 @@ __global__ __launch_bounds__(256) void mix_loss_bwd_kernel(const chap_mix_loss_p
         }
     }
 }
+template <int C>
+__global__ __launch_bounds__(256) void mix_loss_bwd_kernel(const chap_mix_loss_params P_) { mix_loss_bwd_body<C>(P_, blockIdx.x, gridDim.x); }
 
-static int loss_blocks(long total) { long b = (total + 255) / 256; return (int)(b < 2048 ? b : 2048); }
-static int loss_slots(long total) { long b = (total + 255) / 256; return (int)(b < CHAP_LOSS_SLOTS ? b : CHAP_LOSS_SLOTS); }   // kernels that leave one partial row per block
+constexpr int LOSS_MAX_BLOCKS = 2048;
+__host__ __device__ inline int loss_blocks(long total) { long b = (total + 255) / 256; return (int)(b < LOSS_MAX_BLOCKS ? b : LOSS_MAX_BLOCKS); }
+__host__ __device__ inline int loss_slots(long total) { long b = (total + 255) / 256; return (int)(b < CHAP_LOSS_SLOTS ? b : CHAP_LOSS_SLOTS); }   // kernels that leave one partial row per block
+
+// Up to four independent mix_loss terms in one launch each: grid (max_t nb_t, nterms), blockIdx.y selects the term, and a term's blocks
+// are the first nb_t of its row -- nb_t, the grid-stride step and the partial-row index are those of the single-term launch, so every
+// sum runs in the same order and the results are bit for bit those of nterms single-term calls.
+template <int C>
+__global__ __launch_bounds__(256) void mix_loss_multi_acc_kernel(const chap_mix_loss_multi_params M) {
+    const chap_mix_loss_params& P_ = M.term[blockIdx.y];
+    const int nb = loss_slots((long)P_.N * P_.P);
+    if ((int)blockIdx.x >= nb) return;
+    mix_loss_acc_body<C>(P_, blockIdx.x, nb);
+}
+__global__ __launch_bounds__(256) void mix_loss_multi_final_kernel(const chap_mix_loss_multi_params M) {
+    const chap_mix_loss_params& P_ = M.term[blockIdx.x];
+    const bool dflt = P_.k_dice == 0.f && P_.k_ce == 0.f;
+    mix_loss_final_body(P_.acc, loss_slots((long)P_.N * P_.P), P_.loss, P_.C, P_.w_a, P_.w_b, P_.smooth, dflt ? 0.5f : P_.k_dice, dflt ? 0.5f : P_.k_ce);
+}
+template <int C>
+__global__ __launch_bounds__(256) void mix_loss_multi_bwd_kernel(const chap_mix_loss_multi_params M) {
+    const chap_mix_loss_params& P_ = M.term[blockIdx.y];
+    const int nb = loss_blocks((long)P_.N * P_.P);
+    if ((int)blockIdx.x >= nb) return;
+    mix_loss_bwd_body<C>(P_, blockIdx.x, nb);
+}
 
 extern "C" int chap_mix_loss_fwd(const chap_mix_loss_params* p, void* stream) {
     CHAP_CHECK_ARG(p && p->logits && p->target_a && p->acc && p->loss, "chap_mix_loss_fwd: null argument");
@@ -198,6 +230,43 @@ extern "C" int chap_mix_loss_bwd(const chap_mix_loss_params* p, void* stream) {
     if (p->C == 4) hipLaunchKernelGGL(mix_loss_bwd_kernel<4>, dim3(nb), dim3(256), 0, (hipStream_t)stream, *p);
     else hipLaunchKernelGGL(mix_loss_bwd_kernel<2>, dim3(nb), dim3(256), 0, (hipStream_t)stream, *p);
     CHAP_LAUNCH_CHECK("chap_mix_loss_bwd");
+    return CHAP_OK;
+}
+
+// The argument checks of the single-term entries for every term, plus what the terms share (C and P).  `bwd`: dlogits instead of loss.
+static int mix_loss_multi_check(const chap_mix_loss_multi_params* m, bool bwd, const char* who) {
+    CHAP_CHECK_ARG(m, "%s: null argument", who);
+    CHAP_CHECK_ARG(m->nterms >= 1 && m->nterms <= 4, "%s: nterms=%d (1..4)", who, m->nterms);
+    for (int t = 0; t < m->nterms; ++t) {
+        const chap_mix_loss_params* p = &m->term[t];
+        CHAP_CHECK_ARG(p->logits && p->target_a && p->acc && (bwd ? (const void*)p->dlogits : (const void*)p->loss), "%s: null argument in term %d", who, t);
+        CHAP_CHECK_ARG(p->C == 4 || p->C == 2, "chap_mix_loss: C=%d (2 or 4 built)", p->C);
+        CHAP_CHECK_ARG(p->C == m->term[0].C && p->P == m->term[0].P, "%s: term %d has C=%d P=%d, term 0 C=%d P=%d (C and P are common)", who, t, p->C, p->P,
+                       m->term[0].C, m->term[0].P);
+        CHAP_CHECK_ARG(p->N > 0 && p->P > 0, "%s: term %d is empty (N=%d P=%d)", who, t, p->N, p->P);
+        CHAP_CHECK_ARG((long)p->N * p->P < (1L << 32), "chap_mix_loss: N*P=%ld exceeds the 32-bit pixel index", (long)p->N * p->P);
+    }
+    return CHAP_OK;
+}
+extern "C" int chap_mix_loss_multi_fwd(const chap_mix_loss_multi_params* m, void* stream) {
+    if (const int rc = mix_loss_multi_check(m, false, "chap_mix_loss_multi_fwd")) return rc;
+    int nb = 0;
+    for (int t = 0; t < m->nterms; ++t) { const int n = loss_slots((long)m->term[t].N * m->term[t].P); nb = n > nb ? n : nb; }
+    hipStream_t s = (hipStream_t)stream;
+    if (m->term[0].C == 4) hipLaunchKernelGGL(mix_loss_multi_acc_kernel<4>, dim3(nb, m->nterms), dim3(256), 0, s, *m);
+    else hipLaunchKernelGGL(mix_loss_multi_acc_kernel<2>, dim3(nb, m->nterms), dim3(256), 0, s, *m);
+    CHAP_LAUNCH_CHECK("chap_mix_loss_multi_fwd");
+    hipLaunchKernelGGL(mix_loss_multi_final_kernel, dim3(m->nterms), dim3(256), 0, s, *m);
+    CHAP_LAUNCH_CHECK("chap_mix_loss_multi_fwd(final)");
+    return CHAP_OK;
+}
+extern "C" int chap_mix_loss_multi_bwd(const chap_mix_loss_multi_params* m, void* stream) {
+    if (const int rc = mix_loss_multi_check(m, true, "chap_mix_loss_multi_bwd")) return rc;
+    int nb = 0;
+    for (int t = 0; t < m->nterms; ++t) { const int n = loss_blocks((long)m->term[t].N * m->term[t].P); nb = n > nb ? n : nb; }
+    if (m->term[0].C == 4) hipLaunchKernelGGL(mix_loss_multi_bwd_kernel<4>, dim3(nb, m->nterms), dim3(256), 0, (hipStream_t)stream, *m);
+    else hipLaunchKernelGGL(mix_loss_multi_bwd_kernel<2>, dim3(nb, m->nterms), dim3(256), 0, (hipStream_t)stream, *m);
+    CHAP_LAUNCH_CHECK("chap_mix_loss_multi_bwd");
     return CHAP_OK;
 }
 

@@ -299,14 +299,54 @@ def mix_loss_bwd(logits, target_a, target_b, mask, w_a, w_b, acc, dlogits, gscal
     L.call("chap_mix_loss_bwd", p, _stream())
 
 
+def _fill_mix_loss(p, logits, target_a, target_b, mask, w_a, w_b, acc, smooth, k_dice, k_ce):
+    p.logits, p.target_a, p.target_b, p.mask = logits.data_ptr(), target_a.data_ptr(), _p(target_b), _p(mask)
+    p.w_a, p.w_b, p.acc = w_a, w_b, acc.data_ptr()
+    p.N, p.C, p.P, p.smooth, p.k_dice, p.k_ce = logits.shape[0], logits.shape[1], logits[0, 0].numel(), smooth, k_dice, k_ce
+
+
+def mix_loss_multi_fwd(terms):
+    """Up to four mix_loss_fwd calls as one launch per kernel.  terms: dicts of mix_loss_fwd's arguments (logits, target_a, target_b, mask,
+    w_a, w_b and optionally smooth, k_dice, k_ce); the class count and the spatial size are common.  Returns [(loss[3], acc)] in the
+    order of the terms, bit for bit what the single-term calls return."""
+    m = L.MixLossMultiParams()
+    m.nterms = len(terms)
+    if not 1 <= len(terms) <= 4:
+        raise ValueError("mix_loss_multi_fwd: %d terms (1..4)" % len(terms))
+    res = []
+    for p, t in zip(m.term, terms):
+        lg = t["logits"]
+        acc = L.hold_empty((1 + L.LOSS_SLOTS) * 2 * (2 + 3 * lg.shape[1]), dtype=torch.float32, device=lg.device)
+        loss = L.hold_empty(3, dtype=torch.float32, device=lg.device)
+        _fill_mix_loss(p, lg, t["target_a"], t.get("target_b"), t.get("mask"), t["w_a"], t["w_b"], acc, t.get("smooth", 1e-10), t.get("k_dice", 0.0), t.get("k_ce", 0.0))
+        p.loss = loss.data_ptr()
+        res.append((loss, acc))
+    L.call("chap_mix_loss_multi_fwd", m, _stream())
+    return res
+
+
+def mix_loss_multi_bwd(terms):
+    """Up to four mix_loss_bwd calls as one launch.  terms: dicts of mix_loss_bwd's arguments (logits, target_a, target_b, mask, w_a, w_b,
+    acc, dlogits and optionally gscale, accumulate, smooth, k_dice, k_ce, gscale_dev)."""
+    m = L.MixLossMultiParams()
+    m.nterms = len(terms)
+    if not 1 <= len(terms) <= 4:
+        raise ValueError("mix_loss_multi_bwd: %d terms (1..4)" % len(terms))
+    for p, t in zip(m.term, terms):
+        _fill_mix_loss(p, t["logits"], t["target_a"], t.get("target_b"), t.get("mask"), t["w_a"], t["w_b"], t["acc"], t.get("smooth", 1e-10),
+                       t.get("k_dice", 0.0), t.get("k_ce", 0.0))
+        p.dlogits, p.gscale, p.accumulate, p.gscale_dev = t["dlogits"].data_ptr(), t.get("gscale", 1.0), int(t.get("accumulate", False)), _p(t.get("gscale_dev"))
+    L.call("chap_mix_loss_multi_bwd", m, _stream())
+
+
 def pseudo_block(logits1, logits2, want_soft=True):
     N, Cc = logits1.shape[0], logits1.shape[1]
     sp = logits1.shape[2:]
     dev = logits1.device
     soft1 = L.hold_empty_like(logits1) if want_soft else None
     soft2 = L.hold_empty_like(logits2) if want_soft else None
-    arg1 = L.hold_empty((N,) + tuple(sp), dtype=torch.int64, device=dev)
-    arg2 = L.hold_empty_like(arg1)
+    arg = L.hold_empty((2 * N,) + tuple(sp), dtype=torch.int64, device=dev)       # both heads' arg-max maps, stacked: one largest_cc call takes the pair (_stacked_pair)
+    arg1, arg2 = arg[:N], arg[N:]
     know = L.hold_empty((N,) + tuple(sp), dtype=torch.float32, device=dev)
     p = L.PseudoParams()
     p.logits1, p.logits2, p.soft1, p.soft2 = logits1.data_ptr(), logits2.data_ptr(), _p(soft1), _p(soft2)
@@ -414,6 +454,26 @@ def box_mix(a, b, out, box):
     p.N, p.H, p.W, p.is_i64 = a.shape[0], a.shape[-2], a.shape[-1], int(a.dtype == torch.int64)
     p.D = a.shape[-3] if box.numel() == 6 else 1
     L.call("chap_box_mix", p, _stream())
+
+
+def bcp_mix(a0, b0, out0, a1, b1, out1, mask, box):
+    """box_mask(mask, box), box_mix(a0, b0, out0, box) and box_mix(a1, b1, out1, box) (fp32 images) as one launch."""
+    p = L.BcpMixParams()
+    for h, (a, b, o) in enumerate(((a0, b0, out0), (a1, b1, out1))):
+        assert a.dtype == b.dtype == o.dtype == torch.float32 and a.shape == b.shape == o.shape and a.shape[-2:] == mask.shape[-2:]
+        p.a[h], p.b[h], p.out[h], p.N[h] = a.data_ptr(), b.data_ptr(), o.data_ptr(), a.shape[0]
+    p.mask, p.box, p.Nm, p.H, p.W = mask.data_ptr(), box.data_ptr(), mask.shape[0], mask.shape[-2], mask.shape[-1]
+    p.D = mask.shape[-3] if box.numel() == 6 else 1
+    L.call("chap_bcp_mix", p, _stream())
+
+
+def _stacked_pair(a, b):
+    """The [2N, ...] tensor that a and b are the two halves of (as pseudo_block returns its arg-max maps), or None."""
+    base = a._base
+    if base is None or b._base is not base or not base.is_contiguous() or base.shape[0] != 2 * a.shape[0] or base.shape[1:] != a.shape[1:]:
+        return None
+    n = a.numel() * a.element_size()
+    return base if (a.shape == b.shape and a.data_ptr() == base.data_ptr() and b.data_ptr() == base.data_ptr() + n) else None
 
 
 def box_mask(mask, box):

@@ -269,6 +269,12 @@ class ChapStep:
         model.swap_grad_buffer(self.grad_both[:n])
         self.grad2 = self.grad_both[n:]
         self.concurrent = bool(a.get("concurrent", True))
+        # `passb_batch`: pass B's runs of small dependent launches as batched ones -- largest-CC over both heads' maps in one call, loss mask + BCP
+        # mixing in one launch, the four mix_loss terms in one launch per kernel (bit-identical results, DESIGN.md section 5 "Pass B's
+        # small launches").  On by default where pass B is a chain of its own beside the VAT chain (`concurrent`), the chain whose end is
+        # the end of the step; the single-stream step keeps the separate calls unless the argument asks for the batched ones.
+        pb = a.get("passb_batch")
+        self.passb_batch = self.concurrent if pb is None else bool(pb)
         # Streams come from PyTorch's per-device pool (32 of them, handed out round-robin): two "new" streams of a long-lived
         # process can be the SAME stream.  The ones of an iteration must differ from each other and from the stream the graph is
         # captured on (pass B on the capture's origin stream would run behind the VAT chain, not beside it), so they are drawn
@@ -483,17 +489,25 @@ class ChapStep:
         nc = a["num_classes"]
         lsub, usub, volume_batch = ctx["lsub"], ctx["usub"], ctx["volume_batch"]
         with torch.no_grad():
-            if a["nms"]:
+            batch = self.passb_batch
+            stacked = ops._stacked_pair(ctx["pseudo_outputs1"], ctx["pseudo_outputs2"]) if (batch and a["nms"]) else None
+            if stacked is not None:             # the components of an image do not depend on its neighbours in the batch: one call for both heads
+                plab = ops.largest_cc(stacked, nc)
+                plab1, plab2 = plab[:plab.shape[0] // 2], plab[plab.shape[0] // 2:]
+            elif a["nms"]:
                 plab1 = ops.largest_cc(ctx["pseudo_outputs1"], nc)
                 plab2 = ops.largest_cc(ctx["pseudo_outputs2"], nc)
             else:
                 plab1, plab2 = ctx["pseudo_outputs1"], ctx["pseudo_outputs2"]
             loss_mask = torch.empty(lsub, *volume_batch.shape[2:], dtype=torch.int64, device=volume_batch.device)
-            ops.box_mask(loss_mask, self.box)
             # BCP mixing (:335-338): net_input_mix = cat(net_input_l, net_input_unl)
             net_input_mix = torch.empty((lsub + usub,) + tuple(volume_batch.shape[1:]), dtype=torch.float32, device=volume_batch.device)
-            ops.box_mix(ctx["img_b"], ctx["uimg_b"], net_input_mix[:lsub], self.box)       # img_b*mask + uimg_b*(1-mask)
-            ops.box_mix(ctx["uimg_a"], ctx["img_a"], net_input_mix[lsub:], self.box)       # uimg_a*mask + img_a*(1-mask)
+            if batch:
+                ops.bcp_mix(ctx["img_b"], ctx["uimg_b"], net_input_mix[:lsub], ctx["uimg_a"], ctx["img_a"], net_input_mix[lsub:], loss_mask, self.box)
+            else:
+                ops.box_mask(loss_mask, self.box)
+                ops.box_mix(ctx["img_b"], ctx["uimg_b"], net_input_mix[:lsub], self.box)       # img_b*mask + uimg_b*(1-mask)
+                ops.box_mix(ctx["uimg_a"], ctx["img_a"], net_input_mix[lsub:], self.box)       # uimg_a*mask + img_a*(1-mask)
         lab_a, lab_b = ctx["lab_a"], ctx["lab_b"]
         plab_a1, plab_b1 = plab1[:usub], plab1[usub:]
         plab_a2, plab_b2 = plab2[:usub], plab2[usub:]
@@ -510,7 +524,20 @@ class ChapStep:
         if split:       # loss_l / loss_u (:352-353) are taken apart: e* holds the unlabeled-supervised parts' gradient
             e1, e2 = torch.empty_like(out_mix1), torch.empty_like(out_mix2)
             eterms = (e1[lsub:], e2[lsub:], e1[:lsub], e2[:lsub])
-        for ti, (lg, dl, img_l, patch_l, unlab) in enumerate(terms):
+        if batch:       # the four terms are independent: one launch per kernel for all of them (with `split`, the dl set and the e set)
+            base = [dict(logits=lg, target_a=img_l, target_b=patch_l, mask=loss_mask) for lg, _, img_l, patch_l, _ in terms]
+            wts = [(0.5, 1.0) if unlab else (1.0, 0.5) for *_, unlab in terms]                   # l_weight=1.0, u_weight=0.5 (:198-203)
+            fwd = ops.mix_loss_multi_fwd([dict(b, w_a=iw, w_b=pw) for b, (iw, pw) in zip(base, wts)])
+            losses = [l for l, _ in fwd]
+            bwd = lambda ws, outs: ops.mix_loss_multi_bwd([dict(b, w_a=w[0], w_b=w[1], acc=acc, dlogits=o) for b, w, (_, acc), o in zip(base, ws, fwd, outs)])
+            if split:
+                wl = [(0.0, pw) if unlab else (iw, 0.0) for (iw, pw), (*_, unlab) in zip(wts, terms)]
+                wu = [(iw, 0.0) if unlab else (0.0, pw) for (iw, pw), (*_, unlab) in zip(wts, terms)]
+                bwd(wl, [t[1] for t in terms])
+                bwd(wu, eterms)
+            else:
+                bwd(wts, [t[1] for t in terms])
+        for ti, (lg, dl, img_l, patch_l, unlab) in enumerate(() if batch else terms):
             iw, pw = (0.5, 1.0) if unlab else (1.0, 0.5)            # l_weight=1.0, u_weight=0.5 (:198-203)
             loss3, acc = ops.mix_loss_fwd(lg, img_l, patch_l, loss_mask, iw, pw)
             if split:   # (loss_image, loss_patch) = (loss_u_out, loss_l_in) for the unlabeled rows, (loss_l_out, loss_u_in) for the labeled ones (:345-349)

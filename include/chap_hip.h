@@ -304,6 +304,11 @@ typedef struct {
 } chap_mix_loss_params;
 int chap_mix_loss_fwd(const chap_mix_loss_params* p, void* stream);
 int chap_mix_loss_bwd(const chap_mix_loss_params* p, void* stream);
+/* Up to four independent terms in one launch per kernel (accumulate, final; backward): bit for bit the results of nterms single-term
+ * calls.  Terms may differ in N, mask / target_b being NULL, weights, k_dice / k_ce, accumulate and gscale_dev; C and P are common. */
+typedef struct { int32_t nterms; chap_mix_loss_params term[4]; } chap_mix_loss_multi_params;
+int chap_mix_loss_multi_fwd(const chap_mix_loss_multi_params* p, void* stream);
+int chap_mix_loss_multi_bwd(const chap_mix_loss_multi_params* p, void* stream);
 
 typedef struct {               /* pass-A block: softmax, argmax, cross CE "knowledge"             */
     const float* logits1; const float* logits2;   /* [N][C][P]                                     */
@@ -348,6 +353,10 @@ typedef struct { const void* a; const void* b; void* out; const int32_t* box; in
 int chap_box_mix(const chap_boxmix_params* p, void* stream);
 typedef struct { int64_t* mask; const int32_t* box; int32_t N, H, W, D; } chap_boxmask_params;
 int chap_box_mask(const chap_boxmask_params* p, void* stream);       /* loss_mask: 0 inside the box, 1 outside */
+/* The BCP block of an iteration in one launch: chap_box_mask on mask [Nm] and chap_box_mix (fp32) on the two halves of the mixed input,
+ * out[h] [N[h]] = inside box ? b[h] : a[h]; element for element what the three calls write. */
+typedef struct { const float* a[2]; const float* b[2]; float* out[2]; int64_t* mask; const int32_t* box; int32_t N[2]; int32_t Nm, H, W, D; } chap_bcpmix_params;
+int chap_bcp_mix(const chap_bcpmix_params* p, void* stream);
 
 /* Largest connected component per (image, class>0), 8-connectivity (skimage.measure.label default),
  * get_ACDC_2DLargestCC (train_ours_2D.py:123-144) without the 72 device->host round trips.
