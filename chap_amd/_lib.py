@@ -141,6 +141,16 @@ class WindowFinParams(C.Structure):
     _fields_ = [("score", _vp), ("cnt", _vp), ("label", _vp), ("C", _i32), ("P", C.c_int64)]
 
 
+class WindowGatherParams(C.Structure):
+    _fields_ = [("volume", _vp), ("origins", _vp), ("patches", _vp), ("npatch", _i32), ("W", _i32), ("H", _i32), ("D", _i32),
+                ("pad_lo", _i32 * 3), ("pw", _i32), ("ph", _i32), ("pd", _i32)]
+
+
+class WindowAccHeadsParams(C.Structure):
+    _fields_ = [("logits", _vp * 2), ("origins", _vp), ("score", _vp), ("cnt", _vp), ("nheads", _i32), ("npatch", _i32), ("C", _i32),
+                ("pw", _i32), ("ph", _i32), ("pd", _i32), ("W", _i32), ("H", _i32), ("D", _i32)]
+
+
 class L2NormParams(C.Structure):
     _fields_ = [("in_", _vp), ("out", _vp), ("N", _i32), ("P", _i32), ("eps", _f32), ("ws", _vp)]
 
@@ -233,6 +243,14 @@ class Augment3dParams(C.Structure):
                 ("label_i64", _i32), ("B", _i32), ("P0", _i32), ("P1", _i32), ("P2", _i32)]
 
 
+class Augment3dPadRecord(C.Structure):
+    _fields_ = [("offset", _i64), ("shape", _i32 * 3), ("corner", _i32 * 3), ("pad", _i32 * 3), ("k", _i32), ("axis", _i32), ("reserved", _i32)]
+
+
+class Augment3dPadParams(C.Structure):
+    _fields_ = Augment3dParams._fields_
+
+
 class GradSimParams(C.Structure):
     _fields_ = [("gl", _vp), ("gu", _vp), ("score", _vp), ("C", _i32), ("K", _i32), ("ema", _f32)]
 
@@ -256,7 +274,8 @@ _SIGS = {  # name -> (restype, params struct or None)
     "chap_diff_mask": DiffMaskParams, "chap_sgd_step": SgdParams,
     "chap_sample_channel_sum": SampleChanSumParams, "chap_channel_drop": ChannelDropParams,
     "chap_fold_perturbed": FoldParams, "chap_grad_sim": GradSimParams, "chap_metrics": MetricsParams,
-    "chap_augment2d": Augment2dParams, "chap_augment3d": Augment3dParams,
+    "chap_augment2d": Augment2dParams, "chap_augment3d": Augment3dParams, "chap_augment3d_padded": Augment3dPadParams,
+    "chap_window_gather": WindowGatherParams, "chap_window_accumulate_heads": WindowAccHeadsParams,
     "chap_mix_loss_multi_fwd": MixLossMultiParams, "chap_mix_loss_multi_bwd": MixLossMultiParams, "chap_bcp_mix": BcpMixParams,
 }
 _SIZE_FNS = {"chap_pack_size": PackParams, "chap_conv_c1_bwd_ws": ConvC1BwdParams, "chap_wgrad_ws": WgradParams,

@@ -493,16 +493,7 @@ extern "C" int chap_kl_fwd_bwd(const chap_kl_params* p, void* stream) {
 
 // =========================================================================================
 // Inference callers (val_2D.py:54-97, test_3D_util.py:14-79): ensemble + softmax + argmax, sliding-window scores.
-constexpr int INFER_MAXC = 8;
-
-__device__ __forceinline__ void softmax_c(float* v, int C) {
-    float m = v[0];
-    for (int c = 1; c < C; ++c) m = fmaxf(m, v[c]);
-    float s = 0.f;
-    for (int c = 0; c < C; ++c) { v[c] = __expf(v[c] - m); s += v[c]; }
-    const float inv = 1.f / s;
-    for (int c = 0; c < C; ++c) v[c] *= inv;
-}
+#include "infer_math.h"      // INFER_MAXC, softmax_c: shared with window3d.hip
 
 __global__ __launch_bounds__(256) void ensemble_argmax_kernel(const chap_ensemble_params P) {
     const long total = (long)P.N * P.P;

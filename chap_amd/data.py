@@ -78,6 +78,26 @@ class VolumeStore(_Store):
     """VolumeStore(images, labels, device): lists of [d, h, w] arrays."""
     ndim = 3
 
+    @classmethod
+    def from_h5_list(cls, root, list_name="train.list", subdir="2018LA_Seg_Training Set", fname="mri_norm2.h5", device="cuda"):
+        """The LA layout the reference spells out (test_LA.py:25-28): `<root>/<list_name>` names the cases,
+        `<root>/<subdir>/<case>/<fname>` holds `image` and `label`.  `store.cases` keeps the names."""
+        try:
+            import h5py
+        except ImportError as e:
+            raise ImportError("VolumeStore.from_h5_list needs h5py to read %s; build the store from arrays instead: "
+                              "VolumeStore(images, labels)" % root) from e
+        with open(os.path.join(root, list_name)) as f:
+            cases = [ln.strip() for ln in f if ln.strip()]
+        images, labels = [], []
+        for c in cases:
+            with h5py.File(os.path.join(root, subdir, c, fname), "r") as h:
+                images.append(h["image"][:])
+                labels.append(h["label"][:])
+        store = cls(images, labels, device)
+        store.cases = cases
+        return store
+
 
 class TwoStreamBatchSampler:
     """Each epoch one permutation of `primary_indices` (the labelled ones) cut into groups of batch_size - secondary_batch_size, each
@@ -145,18 +165,23 @@ class DeviceLoader:
     yields one epoch of {'image': fp32 [B, 1, *output_size], 'label': int64 [B, *output_size]} DEVICE tensors (fresh tensors, written on the
     current stream); `next_into(image_out, label_out)` writes the next batch of the endless sequence of epochs into caller-owned
     buffers on the current stream (ChapStep.stage_from).  `last_draws`: the draws of the last batch, one dict per sample.
-    A VolumeStore gives the 3D transform with output_size = the patch [P0, P1, P2]."""
+    A VolumeStore gives the 3D transform with output_size = the patch [P0, P1, P2].  `pad=True` (VolumeStore only): a volume with an axis
+    not larger than the crop is zero-padded on every axis before the crop (the public LA RandomCrop rule, DESIGN.md "3D workflow")
+    instead of being refused; the draws then carry a `pad` tuple and `corner` is in padded coordinates."""
     RING = 4
 
-    def __init__(self, store, labeled_idxs, unlabeled_idxs, batch_size, labeled_bs, output_size, seed=0):
+    def __init__(self, store, labeled_idxs, unlabeled_idxs, batch_size, labeled_bs, output_size, seed=0, pad=False):
         self.store, self.batch_size, self.labeled_bs = store, int(batch_size), int(labeled_bs)
+        self.pad = bool(pad)
+        if self.pad and store.ndim != 3:
+            raise ValueError("DeviceLoader: pad=True is the 3D crop's padding; the store is %dD" % store.ndim)
         self.output_size = tuple(int(s) for s in output_size)
         if len(self.output_size) != store.ndim:
             raise ValueError("DeviceLoader: output_size %s for a %dD store" % (self.output_size, store.ndim))
         for i in list(labeled_idxs) + list(unlabeled_idxs):
             if not 0 <= i < len(store):
                 raise IndexError("DeviceLoader: index %d outside the store of %d items" % (i, len(store)))
-        if store.ndim == 3:
+        if store.ndim == 3 and not self.pad:
             # a crop has the patch shape or, after an odd number of quarter turns, the patch with its first two sides swapped
             p = self.output_size
             need = (max(p[0], p[1]), max(p[0], p[1]), p[2])
@@ -166,11 +191,13 @@ class DeviceLoader:
                                  % (small[0], tuple(store.shapes[small[0]]), need, p))
         self.sampler = TwoStreamBatchSampler(labeled_idxs, unlabeled_idxs, batch_size, self.batch_size - self.labeled_bs, seed)
         self.rng = np.random.default_rng([int(seed), 1])          # the augmentation draws: a stream of their own
-        self._rec_t = L.Augment2dRecord if store.ndim == 2 else L.Augment3dRecord
+        self._rec_t = L.Augment2dRecord if store.ndim == 2 else (L.Augment3dPadRecord if self.pad else L.Augment3dRecord)
         nbytes = ctypes.sizeof(self._rec_t) * self.batch_size
         # the record table: a ring of pinned host blocks, each with a device block of its own; a slot is rewritten only after the
         # launch that last read it has run (event), as ChapStep._upload_sched does for the schedule block
-        self._pin = [torch.empty(nbytes, dtype=torch.uint8).pin_memory() for _ in range(self.RING)]
+        # a host-resident store is DRAW-ONLY (the CPU checks of the draws use it: pinning needs a GPU); _launch refuses it by name
+        on_gpu = self.store.device.type == "cuda"
+        self._pin = [torch.empty(nbytes, dtype=torch.uint8).pin_memory() if on_gpu else None for _ in range(self.RING)]
         self._dev = [torch.empty(nbytes, dtype=torch.uint8, device=store.device) for _ in range(self.RING)]
         self._ev, self._slot = [None] * self.RING, 0
         self._endless = self._eternal()
@@ -216,17 +243,26 @@ class DeviceLoader:
                 k, axis = int(self.rng.integers(0, 4)), int(self.rng.integers(0, 2))
                 p = self.output_size
                 crop = (p[1], p[0], p[2]) if k % 2 else p
-                corner = tuple(int(self.rng.integers(0, int(st.shapes[i][a]) - crop[a] + 1)) for a in range(3))
+                sh = [int(v) for v in st.shapes[i]]
+                pad = (0, 0, 0)
+                if self.pad and any(sh[a] <= crop[a] for a in range(3)):      # RandomCrop: one small axis pads all three
+                    pad = tuple(max((crop[a] - sh[a]) // 2 + 3, 0) for a in range(3))
+                corner = tuple(int(self.rng.integers(0, sh[a] + 2 * pad[a] - crop[a] + 1)) for a in range(3))
                 d = dict(index=int(i), corner=corner, k=k, axis=axis)
                 for a in range(3):
-                    r.shape[a], r.corner[a] = int(st.shapes[i][a]), corner[a]
+                    r.shape[a], r.corner[a] = sh[a], corner[a]
                 r.k, r.axis = k, axis
+                if self.pad:
+                    d["pad"] = pad
+                    r.pad[0], r.pad[1], r.pad[2] = pad
             draws.append(d)
         return recs, draws
 
     def _launch(self, idxs, image_out, label_out):
         if len(idxs) != self.batch_size or image_out.shape[0] != self.batch_size or tuple(image_out.shape[2:]) != self.output_size:
             raise ValueError("DeviceLoader: output buffer %s for batches of %d x %s" % (tuple(image_out.shape), self.batch_size, self.output_size))
+        if self._pin[0] is None:
+            raise RuntimeError("DeviceLoader: the store lives on %s; batches are built by a GPU kernel (a host-resident store serves _draw only)" % self.store.device)
         recs, draws = self._draw(idxs)
         k = self._slot
         self._slot = (k + 1) % self.RING
@@ -234,7 +270,7 @@ class DeviceLoader:
             self._ev[k].synchronize()
         ctypes.memmove(self._pin[k].data_ptr(), ctypes.addressof(recs), ctypes.sizeof(recs))
         self._dev[k].copy_(self._pin[k], non_blocking=True)
-        fn = ops.augment2d if self.store.ndim == 2 else ops.augment3d
+        fn = ops.augment2d if self.store.ndim == 2 else (ops.augment3d_padded if self.pad else ops.augment3d)
         fn(self.store.images, self.store.labels, self._dev[k], image_out, label_out)
         ev = torch.cuda.Event()
         ev.record()

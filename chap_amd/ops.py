@@ -557,6 +557,47 @@ def window_accumulate(logits, origins, score, cnt):
     L.call("chap_window_accumulate", p, _stream())
 
 
+def window_gather(volume, origins, patch_size, pad_lo=(0, 0, 0), out=None):
+    """chap_window_gather: volume fp32 [W, H, D] (unpadded); origins int32 device [K, 3] in padded coordinates; returns (or fills
+    `out`) patches fp32 [K, 1, pw, ph, pd], zero where a patch reaches into the padding."""
+    K = origins.shape[0]
+    pw, ph, pd = (int(v) for v in patch_size)
+    assert volume.dtype == torch.float32 and volume.dim() == 3 and volume.is_contiguous()
+    assert origins.dtype == torch.int32 and origins.dim() == 2 and origins.shape[1] == 3 and origins.is_contiguous()
+    if out is None:
+        out = L.hold_empty((K, 1, pw, ph, pd), dtype=torch.float32, device=volume.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (K, 1, pw, ph, pd)
+    p = L.WindowGatherParams()
+    p.volume, p.origins, p.patches, p.npatch = volume.data_ptr(), origins.data_ptr(), out.data_ptr(), K
+    p.W, p.H, p.D = volume.shape
+    p.pad_lo[0], p.pad_lo[1], p.pad_lo[2] = (int(v) for v in pad_lo)
+    p.pw, p.ph, p.pd = pw, ph, pd
+    L.call("chap_window_gather", p, _stream())
+    return out
+
+
+def window_accumulate_heads(logits, origins, score, cnt):
+    """chap_window_accumulate_heads: `logits` a tensor or a list of one or two fp32 [K, C, pw, ph, pd] tensors (the heads of one batch
+    of patches); two heads add the mean of their soft-maxes; otherwise as window_accumulate."""
+    heads = [logits] if isinstance(logits, torch.Tensor) else list(logits)
+    if len(heads) not in (1, 2) or any(h.shape != heads[0].shape or h.dtype != torch.float32 or not h.is_contiguous() for h in heads):
+        raise ValueError("window_accumulate_heads: one or two contiguous fp32 logits tensors of one shape")
+    K, Cc = heads[0].shape[0], heads[0].shape[1]
+    dev = heads[0].device
+    assert origins.dtype == torch.int32 and tuple(origins.shape) == (K, 3) and origins.is_contiguous() and origins.device == dev
+    assert cnt.dtype == torch.float32 and cnt.dim() == 3 and cnt.is_contiguous() and cnt.device == dev
+    assert score.dtype == torch.float32 and tuple(score.shape) == (Cc,) + tuple(cnt.shape) and score.is_contiguous() and score.device == dev
+    assert all(t.device == dev for t in heads)
+    p = L.WindowAccHeadsParams()
+    for h, t in enumerate(heads):
+        p.logits[h] = t.data_ptr()
+    p.origins, p.score, p.cnt = origins.data_ptr(), score.data_ptr(), cnt.data_ptr()
+    p.nheads, p.npatch, p.C = len(heads), heads[0].shape[0], heads[0].shape[1]
+    p.pw, p.ph, p.pd = heads[0].shape[2:]
+    p.W, p.H, p.D = cnt.shape
+    L.call("chap_window_accumulate_heads", p, _stream())
+
+
 def window_finalize(score, cnt):
     """score /= cnt in place; returns label uint8 [W, H, D] = argmax over classes."""
     p = L.WindowFinParams()
@@ -619,3 +660,17 @@ def augment3d(images, labels, records, image_out, label_out):
     p.image_out, p.label_out, p.label_i64 = image_out.data_ptr(), label_out.data_ptr(), int(label_out.dtype == torch.int64)
     p.B, p.P0, p.P1, p.P2 = B, P0, P1, P2
     L.call("chap_augment3d", p, _stream())
+
+
+def augment3d_padded(images, labels, records, image_out, label_out):
+    """chap_augment3d_padded: augment3d with B chap_augment3d_pad_record (corner in padded coordinates, per-axis zero padding)."""
+    B, _, P0, P1, P2 = image_out.shape
+    assert images.dtype == torch.float32 and labels.dtype == torch.uint8 and images.numel() == labels.numel()
+    assert image_out.dtype == torch.float32 and image_out.is_contiguous() and label_out.is_contiguous()
+    assert label_out.dtype in (torch.int64, torch.uint8) and tuple(label_out.shape) == (B, P0, P1, P2)
+    assert records.numel() * records.element_size() >= B * L.C.sizeof(L.Augment3dPadRecord)
+    p = L.Augment3dPadParams()
+    p.images, p.labels, p.store_elems, p.records = images.data_ptr(), labels.data_ptr(), images.numel(), records.data_ptr()
+    p.image_out, p.label_out, p.label_i64 = image_out.data_ptr(), label_out.data_ptr(), int(label_out.dtype == torch.int64)
+    p.B, p.P0, p.P1, p.P2 = B, P0, P1, P2
+    L.call("chap_augment3d_padded", p, _stream())

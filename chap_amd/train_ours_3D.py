@@ -1,0 +1,118 @@
+"""train(args, snapshot_path) for the 3D configuration (LA, V-Net DualDecoder3d, 112 x 112 x 80 patches): the host loop of
+chap_amd/train_ours_2D.py around the same captured iteration (ChapStep, dims 3).  Upstream has no 3D training script (SURVEY
+section 1.5): the loop, its outputs (`latest.pth`, `{model}_best_model.pth`, `val.csv`, `log.txt`) and its flags are those of
+code/train_ours_2D.py:219-463; the data layer and the validation are this project's definition (DESIGN.md "3D workflow", unpinned).
+
+Data, the first that is present: `args["trainloader"]` (any iterable of {'image': [B,1,P0,P1,P2] fp32, 'label': [B,P0,P1,P2]} dicts; a
+loader with `next_into`, chap_amd.data.DeviceLoader, feeds the captured iteration through ChapStep.stage_from); `args["root_path"]` +
+`args["labeled_num"]` (the LA h5 layout of test_LA.py:25-28: the first `labeled_num` cases of `train.list` are the labelled ones,
+volumes resident on the device, random crops zero-padded where a volume is smaller than the patch); else the fixed-seed synthetic
+generator.  Validation: `args["val_volumes"]`, a list of (image [w,h,d], label [w,h,d]) arrays, scored by the sliding window of
+chap_amd.test_3d_patch.var_all_case (mean foreground Dice, first decoder).  `dropout=True` is unsupported in 3D (ChapStep raises)."""
+import csv
+import logging
+import os
+import time
+
+import numpy as np
+import torch
+
+from .networks.net_factory_3d import net_factory_3d
+from .synthetic import synthetic_batch_3d
+from .test_3d_patch import var_all_case
+from .train import DEFAULT_ARGS, ChapStep
+
+FLAG_DEFAULTS = dict(DEFAULT_ARGS, model="dualdecoder", num_classes=2, patch_size=[112, 112, 80], batch_size=4, labeled_bs=2,
+                     stride_xy=18, stride_z=4, val_interval=200, use_graph=True, gpu=0, seed=1337)
+
+
+def _synthetic_loader(a):
+    lbs, ubs = a["labeled_bs"], a["batch_size"] - a["labeled_bs"]
+    pool = [synthetic_batch_3d(a["seed"] + i, lbs, ubs, *a["patch_size"]) for i in range(4)]
+    while True:
+        for v, l in pool:
+            yield {"image": v, "label": l}
+
+
+def train(args, snapshot_path):
+    a = dict(FLAG_DEFAULTS)
+    a.update(args)
+    os.makedirs(snapshot_path, exist_ok=True)
+    log = logging.getLogger("chap_amd.train3d")
+    log.setLevel(logging.INFO)
+    fh = logging.FileHandler(os.path.join(snapshot_path, "log.txt"))
+    log.addHandler(fh)
+    try:
+        device = torch.device("cuda", a["gpu"])
+        torch.manual_seed(a["seed"])
+        np.random.seed(a["seed"])
+        model = net_factory_3d(net_type=a["model"], in_chns=1, class_num=a["num_classes"], mode="train", device=device, args=a)
+        if model is None:
+            raise ValueError("chap_amd.train_ours_3D: no 3D network named %r" % (a["model"],))
+        model.train()
+        if a.get("dtype", "fp32") == "bf16":
+            model.set_compute_dtype(torch.bfloat16)
+        step = ChapStep(model, a)
+        loader = a.get("trainloader")
+        if loader is None and a.get("root_path") and a.get("labeled_num"):
+            from .data import DeviceLoader, VolumeStore
+            store = VolumeStore.from_h5_list(a["root_path"], device=device)
+            n_lab = int(a["labeled_num"])
+            loader = DeviceLoader(store, range(n_lab), range(n_lab, len(store)), a["batch_size"], a["labeled_bs"], a["patch_size"], a["seed"], pad=True)
+        loader = loader or _synthetic_loader(a)
+        device_fed = a["use_graph"] and hasattr(loader, "next_into")      # the next batch is built on the device, beside the running iteration
+        val = a.get("val_volumes")
+        if val is None:
+            vi, vl = synthetic_batch_3d(a["seed"] + 4242, 1, 0, *a["patch_size"])
+            val = [(vi[0, 0].numpy(), vl[0].numpy())]
+        best, captured = 0.0, False
+
+        def batches():
+            """train_ours_2D.py:299-302, 459-463: a finite loader is re-iterated until max_iterations is reached; one that yields nothing ends
+            the run, loudly."""
+            while True:
+                n = 0
+                for b in loader:
+                    n += 1
+                    yield b
+                if n == 0:
+                    raise RuntimeError("chap_amd.train_ours_3D: the train loader yielded no batch (exhausted one-shot iterator or empty dataset) "
+                                       "at iteration %d of %d" % (step.iter_num, a["max_iterations"]))
+
+        gen = batches()
+        sampled_batch = next(gen)
+        while True:
+            if a["use_graph"]:
+                if not captured:
+                    step.capture(sampled_batch["image"].to(device), sampled_batch["label"].to(device))
+                    captured = True
+                    step.stage(sampled_batch["image"], sampled_batch["label"])
+                out = step.replay()
+            else:
+                out = step.step(sampled_batch["image"].to(device, non_blocking=True), sampled_batch["label"].to(device, non_blocking=True))
+            it = step.iter_num
+            if it % 50 == 0:
+                log.info("iteration %d : bcp loss : %f vat loss : %f" % (it, sum(float(l[2]) for l in out["mix_losses"]), float(out["vat_loss"])))
+            if it > 0 and it % a["val_interval"] == 0:
+                model.eval()
+                dice = float(var_all_case(model, val, a["num_classes"], tuple(a["patch_size"]), a["stride_xy"], a["stride_z"]))
+                torch.save(model.state_dict(), os.path.join(snapshot_path, "latest.pth"))
+                if dice > best:
+                    best = dice
+                    torch.save(model.state_dict(), os.path.join(snapshot_path, "{}_best_model.pth".format(a["model"])))
+                    with open(os.path.join(snapshot_path, "val.csv"), "a", newline="") as f:
+                        csv.writer(f).writerow([time.strftime("%Y-%m-%d %H:%M:%S"), it, round(best, 4)])
+                log.info("iteration %d : dice_score : %f" % (it, dice))
+                model.train()
+            if it >= a["max_iterations"]:
+                break
+            if device_fed:
+                step.stage_from(loader)
+                continue
+            sampled_batch = next(gen)
+            if a["use_graph"]:
+                step.stage(sampled_batch["image"], sampled_batch["label"])      # travels while the iteration enqueued above runs
+    finally:                    # also when the loop raises: a later train() in this process must not log into this file
+        log.removeHandler(fh)
+        fh.close()
+    return model

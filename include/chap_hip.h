@@ -44,6 +44,8 @@
  *      tensors).
  *      Additive, no version change: chap_metrics / chap_metrics_ws (segmentation metrics, new structs only).
  *      Additive, no version change: chap_augment2d / chap_augment3d (device-resident training input, new structs only).
+ *      Additive, no version change: chap_window_gather / chap_window_accumulate_heads / chap_augment3d_padded (the 3D workflow: device-side
+ *      sliding-window patches, one- or two-head score accumulation, zero-padded training crops; new structs only).
  *   9  (8 was the in-launch BatchNorm finalize, withdrawn before any release) chap_diffmask_params carries the integer count k instead of the float fraction topk: the library computed (int)(topk_f32 * (float)M),
  *      one more than the definition's max(int(topk * M), 1) in double for e.g. topk = 0.29, M = 100.  The caller computes k.
  */
@@ -401,6 +403,27 @@ int chap_window_accumulate(const chap_window_acc_params* p, void* stream);
 typedef struct { float* score; const float* cnt; uint8_t* label; int32_t C; int64_t P; } chap_window_fin_params;
 int chap_window_finalize(const chap_window_fin_params* p, void* stream);
 
+/* chap_window_gather: the patches of a sliding window, cut on the device -- what test_3D_util.py:33-34 (np.pad of the volume) and
+ * :59-61 (the slice, two expand_dims, the upload) do on the host per window.  volume fp32 [W][H][D], UNPADDED; pad_lo: voxels of
+ * virtual zero padding in front of each axis; origins int32 device [npatch][3] in PADDED coordinates;
+ *     patches[k][0][i][j][l] = volume[o_k + (i, j, l) - pad_lo]   where that index lies inside the volume, else 0.0f.
+ * Any origin is legal (what falls outside reads as padding).  A copy: bit-exact.  16-byte stores along pd when pd % 4 == 0 and
+ * `patches` is 16-byte aligned, scalar stores otherwise.  npatch <= 65535. */
+typedef struct { const float* volume; const int32_t* origins; float* patches /* [npatch][1][pw][ph][pd] */;
+                 int32_t npatch; int32_t W, H, D; int32_t pad_lo[3]; int32_t pw, ph, pd; } chap_window_gather_params;
+int chap_window_gather(const chap_window_gather_params* p, void* stream);
+
+/* chap_window_accumulate_heads: chap_window_accumulate for the nheads in {1, 2} logits tensors a network returned for the same
+ * batch of patches (test_3D_util.py:62-69 with the head average the absent utils/test_3d_patch.py applies for num_outputs > 1,
+ * call site test_LA.py:50-58).  Per voxel and covering patch, in patch order k:
+ *     nheads 1: score += softmax_c(logits[0])                 -- bit for bit chap_window_accumulate;
+ *     nheads 2: score += fl(fl(p1 + p2) / 2), p_h = softmax_c(logits[h])   -- the arithmetic of chap_ensemble_argmax mode 3;
+ * cnt += 1 per covering patch (not per head).  Voxels no patch covers are left untouched.  Gather form, no float atomics.
+ * chap_window_finalize finishes the map. */
+typedef struct { const float* logits[2] /* fp32 [npatch][C][pw][ph][pd] each; [1] unused when nheads == 1 */; const int32_t* origins;
+                 float* score; float* cnt; int32_t nheads, npatch, C; int32_t pw, ph, pd; int32_t W, H, D; } chap_window_acc_heads_params;
+int chap_window_accumulate_heads(const chap_window_acc_heads_params* p, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Segmentation metrics: what medpy.metric.binary dc / jc / ravd / hd / hd95 / asd / assd need, for K classes of
  * one pair of maps in one launch chain (callers: val_2D.py:43-51, test_2D_fully.py:37-51, test_3D_util.py:82-88,147-152).
@@ -495,6 +518,30 @@ typedef struct {
     int32_t B, P0, P1, P2;
 } chap_augment3d_params;
 int chap_augment3d(const chap_augment3d_params* p, void* stream);
+
+/* chap_augment3d with per-sample zero padding (the public LA RandomCrop pads a volume that is not larger than the crop on every axis,
+ * np.pad mode='constant'; the project's own definition as above, unpinned): the crop is taken from the volume surrounded by pad[a]
+ * zero voxels on both sides of axis a.  corner is in PADDED coordinates; crop voxel s reads source t = corner + s - pad per axis, inside
+ * iff 0 <= t < shape on all three axes, else image 0.0f and label 0.  The rot90 / flip index maps are chap_augment3d's.  The host
+ * guarantees pad >= 0, corner >= 0 and corner + crop <= shape + 2 * pad; a sample whose record violates that, or whose offset leaves the
+ * store, is zero-filled.  With pad == 0 the output is chap_augment3d's bit for bit. */
+typedef struct {
+    int64_t offset;                /* first element of the source volume                                              */
+    int32_t shape[3];              /* its shape                                                                       */
+    int32_t corner[3];             /* first voxel of the crop, padded coordinates                                     */
+    int32_t pad[3];                /* zero voxels in front of (and behind) each axis                                  */
+    int32_t k, axis;
+    int32_t reserved;
+} chap_augment3d_pad_record;
+typedef struct {
+    const float* images; const uint8_t* labels; int64_t store_elems;
+    const chap_augment3d_pad_record* records;   /* device [B]                                                         */
+    float* image_out;              /* [B][1][P0][P1][P2] fp32                                                         */
+    void*  label_out;              /* [B][P0][P1][P2] int64 or uint8                                                  */
+    int32_t label_i64;
+    int32_t B, P0, P1, P2;
+} chap_augment3d_pad_params;
+int chap_augment3d_padded(const chap_augment3d_pad_params* p, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Channel-level perturbation: FilterDropout.perform_dropout (FilterDropout.py:45-89) as two kernels.
