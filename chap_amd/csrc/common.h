@@ -4,15 +4,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
-#include "chap_hip.h"
+#include "host.h"
+#include "knobs.h"
 
 typedef uint16_t bf16_t;
 typedef __attribute__((ext_vector_type(8))) short s16x8;   // 8 x bf16 MFMA operand (4 VGPRs)
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
-void chap_set_error(const char* fmt, ...);
-#define CHAP_CHECK_ARG(cond, ...) do { if (!(cond)) { chap_set_error(__VA_ARGS__); return CHAP_EINVAL; } } while (0)
 bool chap_group_recording();      // launch.h: true between chap_group_begin() and chap_group_end()
 // after a DIRECT launch (kernels that are not behind launch.h's trampoline): inside a group region it would have overtaken the
 // recorded launches, which is an error of the caller
@@ -146,13 +145,9 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
-static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
-
 // Grid of a grid-stride streaming kernel: ceil(units / 256) blocks, capped.  CHAP_GRID_SCALE (lab knob, per cent) scales every cap.
 static inline int chap_blocks(long units, long cap) {
-    static int scale = -1;
-    if (scale < 0) { const char* e = getenv("CHAP_GRID_SCALE"); scale = (e && atoi(e) > 0) ? atoi(e) : 100; }
-    long c = cap * scale / 100;
+    long c = cap * chap_knob(KNOB_GRID_SCALE) / 100;
     if (c < 64) c = 64;
     const long b = (units + 255) / 256;
     return (int)(b < c ? (b > 0 ? b : 1) : c);

@@ -11,7 +11,7 @@
 //
 // Same operands, packed-weight layout, lazy-activation prologue (BN affine, LeakyReLU, Dropout keep masks, Dropout3d channel
 // multipliers, two concatenated sources), statistics slots and bit-level output conventions as conv_fwd_kernel; built for the
-// plain channel-last output (no depth-to-space, no planar logits, no skip add) -- conv_api.hip routes everything else to
+// plain channel-last output (no depth-to-space, no planar logits, no skip add) -- conv_make_plan (conv_plan.h) routes everything else to
 // conv_fwd_kernel.
 #pragma once
 #include "conv_kernel.h"

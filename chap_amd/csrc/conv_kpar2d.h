@@ -65,7 +65,7 @@ __device__ __forceinline__ void halo_issue_round(halo_regs<T, UNITS, false, KEEP
 //     fragments per dx for 3 * RW MFMA rows -- 30 LDS reads per chunk instead of 72 (the loop was LDS-read bound at twice its MFMA time).
 // SINGLE (one round: <= 128 input channels): the accumulators are not live while the halos are staged, which is what leaves room for the weight
 // fragments beside them; layers with two rounds (256 channels) request each round's weight fragments behind its staging.
-// Same operands, statistics slots and output conventions as conv_kpar_kernel; conv_api.hip routes (2D, k3 s1, 32-channel chunks, plain output).
+// Same operands, statistics slots and output conventions as conv_kpar_kernel; conv_make_plan (conv_plan.h) routes (2D, k3 s1, 32-channel chunks, plain output).
 template <int NT, int CPAR, bool ONE, bool KEEPM, bool SINGLE>
 __device__ __forceinline__ void conv_kpar2d_kernel(const chap_conv_params& P) {      // runs behind chap_grouped<.., 256, 2> (launch.h)
     typedef bf16_t T;

@@ -9,7 +9,9 @@
 // bit-identical results to the one-by-one launches, with one fixed cost instead of 2-4.  Lanes that do not match are launched one
 // after the other in lane order.  (include/chap_hip.h: chap_group_begin / chap_group_next_lane / chap_group_end.)
 #pragma once
+#include <atomic>
 #include <cstring>
+#include <mutex>
 #include <type_traits>
 #include "common.h"
 
@@ -123,3 +125,28 @@ static int chap_launch_z(dim3 grid, dim3 block, size_t lds, hipStream_t s, const
 // entry points whose kernels are launched directly (not through chap_launch) must not be called inside a group region: their
 // launch would overtake the recorded ones
 #define CHAP_NOT_IN_GROUP(name) do { if (chap_group_recording()) { chap_set_error("%s: not allowed between chap_group_begin() and chap_group_end()", name); return CHAP_EUNSUPPORTED; } } while (0)
+
+// ---- per-device launch caches -------------------------------------------------------------
+constexpr int CHAP_MAX_DEVICES = 16;      // per-device caches of the launchers: devices beyond share slot 0's
+static inline int chap_device() {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= CHAP_MAX_DEVICES) dev = 0;
+    return dev;
+}
+
+// Dynamic LDS above 48 KB needs the kernel's MaxDynamicSharedMemorySize attribute raised first.  One cache per kernel instance (a static of
+// its launcher) holds, per device, the largest size the attribute was raised to: the fast path reads one atomic word, the slow path (first
+// launch of an instance on a device, or a larger request) runs under a mutex.  The first raise of an instance happens in warm-up launches,
+// never for the first time under stream capture.  Launchers with one fixed LDS size per instance raise at most once.
+struct chap_lds_cache { std::atomic<size_t> raised[CHAP_MAX_DEVICES]; };
+static inline int chap_raise_lds(chap_lds_cache& c, int dev, const void* kern, size_t lds, const char* who) {
+    if (lds <= 48 * 1024 || lds <= c.raised[dev].load(std::memory_order_acquire)) return CHAP_OK;
+    static std::mutex slow;
+    std::lock_guard<std::mutex> lk(slow);
+    if (lds > c.raised[dev].load(std::memory_order_relaxed)) {
+        hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) { chap_set_error("%s: hipFuncSetAttribute(%zu) failed: %s", who, lds, hipGetErrorString(e)); return CHAP_ELAUNCH; }
+        c.raised[dev].store(lds, std::memory_order_release);
+    }
+    return CHAP_OK;
+}

@@ -87,9 +87,7 @@ extern "C" int chap_conv_c1_fwd(const chap_conv_c1_params* p, void* stream) {
     const bool d3 = p->dims == 3, bf = p->dtype == CHAP_BF16;
     if (bf) {
         // bf16: the taps as the K dimension of one MFMA per 16 pixels (conv_c1_mfma.h).  CHAP_C1_MFMA=0 (lab knob): the scalar kernel below.
-        static int mf = -1;
-        if (mf < 0) { const char* e = getenv("CHAP_C1_MFMA"); mf = (e && atoi(e) == 0) ? 0 : 1; }
-        if (mf) {
+        if (chap_knob(KNOB_C1_MFMA) != 0) {
             CHAP_CHECK_ARG(npix < (1l << 31), "chap_conv_c1_fwd: %ld pixels", npix);
             auto waste = [&](int txt) { const int tx = 16 * txt; return cdiv(p->W, tx) * tx - p->W; };
             const int txt = waste(5) < waste(4) ? 5 : 4;         // 16-pixel tiles per block row: W = 80 (LA patches) takes 5, powers of two 4
@@ -307,9 +305,7 @@ __device__ __forceinline__ void bn_finalize_kernel(const chap_bn_finalize_params
 extern "C" int chap_bn_finalize(const chap_bn_finalize_params* p, void* stream) {
     CHAP_CHECK_ARG(p && p->stats && p->gamma && p->beta && p->scale && p->shift && p->C > 0 && p->count > 0, "chap_bn_finalize: bad argument");
     CHAP_CHECK_ARG(p->Clog >= p->C && p->Clog % p->C == 0, "chap_bn_finalize: Clog=%d must be a multiple of C=%d", p->Clog, p->C);
-#ifdef CHAP_LAB      // lab builds only (tools/lab, loaded through CHAP_LIBPATH): timing bound, wrong numerics
-    { static int skip = -1; if (skip < 0) skip = getenv("CHAP_LAB_SKIP_BNFIN") ? 1 : 0; if (skip) return CHAP_OK; }
-#endif
+    if (chap_lab_skip(KNOB_LAB_SKIP_BNFIN)) return CHAP_OK;      // lab builds only (tools/lab, loaded through CHAP_LIBPATH): timing bound, wrong numerics
     return chap_launch<chap_bn_finalize_params, bn_finalize_kernel, 256>(dim3(cdiv(p->C, 4)), dim3(256), 0, (hipStream_t)stream, *p, "chap_bn_finalize");
 }
 
@@ -360,9 +356,7 @@ __device__ __forceinline__ void act_pool2_kernel(const chap_pool_params& P) {
 extern "C" int chap_act_pool2(const chap_pool_params* p, void* stream) {
     CHAP_CHECK_ARG(p && p->r.ptr && p->out, "chap_act_pool2: null argument");
     CHAP_CHECK_ARG(p->r.C % 8 == 0 && p->H % 2 == 0 && p->W % 2 == 0 && (p->D <= 1 || p->D % 2 == 0), "chap_act_pool2: C%%8, even dims required");
-#ifdef CHAP_LAB      // lab builds only: timing bound (wrong numerics) of fusing this launch into its consumer
-    { static int skip = -1; if (skip < 0) skip = getenv("CHAP_LAB_SKIP_POOL") ? 1 : 0; if (skip) return CHAP_OK; }
-#endif
+    if (chap_lab_skip(KNOB_LAB_SKIP_POOL)) return CHAP_OK;      // lab builds only: timing bound (wrong numerics) of fusing this launch into its consumer
     const long total = (long)p->N * (p->D > 1 ? p->D / 2 : 1) * (p->H / 2) * (p->W / 2) * (p->r.C / 8);
     const int blocks = chap_blocks(total, 4096);
     if (p->dtype == CHAP_BF16) return chap_launch<chap_pool_params, act_pool2_kernel<bf16_t>, 256>(dim3(blocks), dim3(256), 0, (hipStream_t)stream, *p, "chap_act_pool2");
@@ -481,9 +475,7 @@ __device__ __forceinline__ void upsample2x_cell_kernel(const chap_upsample_param
 extern "C" int chap_upsample2x(const chap_upsample_params* p, void* stream) {
     CHAP_CHECK_ARG(p && p->r.ptr && p->out && p->r.C % 8 == 0, "chap_upsample2x: bad argument");
     CHAP_CHECK_ARG(p->out_ld % 8 == 0 && p->out_coff % 8 == 0, "chap_upsample2x: out_ld/out_coff must be multiples of 8");
-#ifdef CHAP_LAB      // lab builds only: timing bound (wrong numerics) of fusing this launch into its consumer
-    { static int skip = -1; if (skip < 0) skip = getenv("CHAP_LAB_SKIP_UPSAMPLE") ? 1 : 0; if (skip) return CHAP_OK; }
-#endif
+    if (chap_lab_skip(KNOB_LAB_SKIP_UPSAMPLE)) return CHAP_OK;      // lab builds only: timing bound (wrong numerics) of fusing this launch into its consumer
     const bool d3 = p->dims == 3;
     if (p->H >= 2 && p->W >= 2 && (!d3 || p->D >= 2)) {
         const long cells = (long)p->N * (d3 ? p->D - 1 : p->D) * (p->H - 1) * (p->W - 1) * (p->r.C / 8);
@@ -569,9 +561,7 @@ __device__ __forceinline__ void upsample2x_bwd_kernel(const chap_upsample_bwd_pa
 }
 extern "C" int chap_upsample2x_bwd(const chap_upsample_bwd_params* p, void* stream) {
     CHAP_CHECK_ARG(p && p->g && p->out && p->C % 8 == 0 && p->g_ld % 8 == 0 && p->g_coff % 8 == 0, "chap_upsample2x_bwd: bad argument");
-#ifdef CHAP_LAB      // lab builds only: timing bound (wrong numerics) of fusing this launch into its consumer
-    { static int skip = -1; if (skip < 0) skip = getenv("CHAP_LAB_SKIP_UPSAMPLE_BWD") ? 1 : 0; if (skip) return CHAP_OK; }
-#endif
+    if (chap_lab_skip(KNOB_LAB_SKIP_UPSAMPLE_BWD)) return CHAP_OK;      // lab builds only: timing bound (wrong numerics) of fusing this launch into its consumer
     const long total = (long)p->N * p->D * p->H * p->W * (p->C / 8);
     const int blocks = chap_blocks(total, 8192);
     if (p->dtype == CHAP_BF16) return chap_launch<chap_upsample_bwd_params, upsample2x_bwd_kernel<bf16_t>, 256>(dim3(blocks), dim3(256), 0, (hipStream_t)stream, *p, "chap_upsample2x_bwd");
@@ -752,8 +742,8 @@ static int act_bwd_blocks(const chap_act_bwd_params* p) {
     // 2 blocks per CU, swept on the whole iteration (round 2, final tree: 256 / 384 / 512 / 640 / 768 / 1024 blocks -> 7.36 / 7.28 / 7.28 / 7.31 /
     // 7.38 / 7.41 ms per 2D step, 3D 16.80-16.87 for all): more blocks add partial rows to total and take CUs from the kernels of the
     // other streams
-    static long cap = 0;
-    if (!cap) { const char* e = getenv("CHAP_ACTBWD_BLOCKS"); cap = (e && atol(e) > 0 && atol(e) <= CHAP_ACT_BWD_SLOTS) ? atol(e) : 512; }      // lab knob
+    long cap = chap_knob(KNOB_ACTBWD_BLOCKS);      // lab knob
+    if (cap > CHAP_ACT_BWD_SLOTS) cap = 512;
     return (int)(b < cap ? b : cap);          // one partial row per block
 }
 extern "C" int chap_act_bwd_reduce(const chap_act_bwd_params* p, void* stream) {
@@ -764,18 +754,14 @@ extern "C" int chap_act_bwd_reduce(const chap_act_bwd_params* p, void* stream) {
     if (p->dtype == CHAP_BF16) r = chap_launch<chap_act_bwd_params, act_bwd_kernel<bf16_t, false>, 256>(dim3(nb), dim3(256), lds, (hipStream_t)stream, *p, "chap_act_bwd_reduce");
     else r = chap_launch<chap_act_bwd_params, act_bwd_kernel<float, false>, 256>(dim3(nb), dim3(256), lds, (hipStream_t)stream, *p, "chap_act_bwd_reduce");
     if (r) return r;
-#ifdef CHAP_LAB      // lab builds only: timing bound, wrong numerics
-    { static int skip = -1; if (skip < 0) skip = getenv("CHAP_LAB_SKIP_ACTSUM") ? 1 : 0; if (skip) return CHAP_OK; }
-#endif
+    if (chap_lab_skip(KNOB_LAB_SKIP_ACTSUM)) return CHAP_OK;      // lab builds only: timing bound, wrong numerics
     const act_bwd_sum_args sa = {p->sums, nb, p->dgamma, p->dbeta, p->r.C};
     return chap_launch<act_bwd_sum_args, act_bwd_sum_kernel, 256>(dim3(cdiv(2 * p->r.C, 4)), dim3(256), 0, (hipStream_t)stream, sa, "chap_act_bwd_reduce(sum)");
 }
 extern "C" int chap_act_bwd_apply(const chap_act_bwd_params* p, void* stream) {
     int r = act_bwd_check(p); if (r) return r;
     CHAP_CHECK_ARG(p->gout, "chap_act_bwd_apply: null gout");
-#ifdef CHAP_LAB      // lab builds only: timing bound (wrong numerics) for folding this pass into the loads of its consumers
-    { static int skip = -1; if (skip < 0) skip = getenv("CHAP_LAB_SKIP_ACTAPPLY") ? 1 : 0; if (skip && p->bn == 1) return CHAP_OK; }
-#endif
+    if (chap_lab_skip(KNOB_LAB_SKIP_ACTAPPLY) && p->bn == 1) return CHAP_OK;      // lab builds only: timing bound (wrong numerics) for folding this pass into the loads of its consumers
     const size_t lds = 2 * p->r.C * sizeof(float);
     if (p->dtype == CHAP_BF16) return chap_launch<chap_act_bwd_params, act_bwd_kernel<bf16_t, true>, 256>(dim3(act_bwd_blocks(p)), dim3(256), lds, (hipStream_t)stream, *p, "chap_act_bwd_apply");
     return chap_launch<chap_act_bwd_params, act_bwd_kernel<float, true>, 256>(dim3(act_bwd_blocks(p)), dim3(256), lds, (hipStream_t)stream, *p, "chap_act_bwd_apply");

@@ -1,5 +1,5 @@
 """Join tools/shape_table.py's plan (--trace-plan) with the rocprofv3 --kernel-trace CSV of the same run: per
-(op, shape) the kernel INSTANCE names and their trace durations.
+(op, shape) the kernel INSTANCE names, their trace durations and (column `launch`) their grid in blocks and LDS bytes.
 
     python tools/shape_join.py <shape_table.csv> <plan.json> <dir-with-*kernel_trace.csv> <out.csv>
 
@@ -29,11 +29,13 @@ MFMA = {"bf16": 2500.0e12, "fp32": 157.3e12}
 outrows = []
 for i, pl in enumerate(plan):
     seg = tr[marks[2 * i] + 1:marks[2 * i + 1]]
-    per = collections.OrderedDict()
+    per, geo = collections.OrderedDict(), {}
     for r in seg:
         per.setdefault(r["Kernel_Name"], []).append(int(r["End_Timestamp"]) - int(r["Start_Timestamp"]))
+        grid = "x".join(str(int(r["Grid_Size_" + a]) // max(int(r["Workgroup_Size_" + a]), 1)) for a in "XYZ")
+        geo.setdefault(r["Kernel_Name"], set()).add("grid=%s lds=%s" % (grid, r["LDS_Block_Size"]))
     # the graph replay holds `reps` launches of each kernel of the op
-    kern = []
+    kern, launch = [], []
     tot_us = 0.0
     for name, ds in per.items():
         if len(ds) < pl["reps"]:
@@ -42,9 +44,11 @@ for i, pl in enumerate(plan):
         us = sum(ds) / 1e3 / pl["reps"]
         tot_us += us
         kern.append("%s = %.2f us" % (short_name(name), us))
+        launch.append("%s: %s" % (short_name(name), ", ".join(sorted(geo[name]))))
     r = dict(by_key[(pl["op"], pl["shape"])])
     r["trace_us"] = round(tot_us, 2)
     r["kernels"] = " | ".join(kern)
+    r["launch"] = " | ".join(launch)
     by, fl = float(r["alg_MB"]) * 1e6, float(r["GFLOP"]) * 1e9
     if tot_us > 0:
         r["trace_hbm_frac"] = round(by / (tot_us * 1e-6) / 8000e9, 4)
