@@ -251,6 +251,20 @@ class Augment3dPadParams(C.Structure):
     _fields_ = Augment3dParams._fields_
 
 
+class ResidualParams(C.Structure):
+    _fields_ = [("r", Src), ("src", Src * 2), ("nsrc", _i32), ("xin", _vp), ("out", _vp),
+                ("N", _i32), ("D", _i32), ("H", _i32), ("W", _i32), ("dtype", _i32)]
+
+
+class ResidualBwdParams(C.Structure):
+    _fields_ = [("g", _vp * 3), ("g_ld", _i32 * 3), ("g_coff", _i32 * 3), ("ng", _i32), ("out", _vp), ("chan_mul", _vp),
+                ("gout", _vp), ("dxin", _vp), ("N", _i32), ("D", _i32), ("H", _i32), ("W", _i32), ("C", _i32), ("dtype", _i32)]
+
+
+class GradSumParams(C.Structure):
+    _fields_ = [("g", _vp * 4), ("g_ld", _i32 * 4), ("g_coff", _i32 * 4), ("ng", _i32), ("out", _vp), ("npix", _i64), ("C", _i32), ("dtype", _i32)]
+
+
 class GradSimParams(C.Structure):
     _fields_ = [("gl", _vp), ("gu", _vp), ("score", _vp), ("C", _i32), ("K", _i32), ("ema", _f32)]
 
@@ -277,6 +291,7 @@ _SIGS = {  # name -> (restype, params struct or None)
     "chap_augment2d": Augment2dParams, "chap_augment3d": Augment3dParams, "chap_augment3d_padded": Augment3dPadParams,
     "chap_window_gather": WindowGatherParams, "chap_window_accumulate_heads": WindowAccHeadsParams,
     "chap_mix_loss_multi_fwd": MixLossMultiParams, "chap_mix_loss_multi_bwd": MixLossMultiParams, "chap_bcp_mix": BcpMixParams,
+    "chap_residual_fwd": ResidualParams, "chap_residual_bwd": ResidualBwdParams, "chap_grad_sum": GradSumParams,
 }
 _SIZE_FNS = {"chap_pack_size": PackParams, "chap_conv_c1_bwd_ws": ConvC1BwdParams, "chap_wgrad_ws": WgradParams,
              "chap_lcc_ws": LccParams, "chap_metrics_ws": MetricsParams}

@@ -22,7 +22,8 @@ BN_MOMENTUM = 0.1
 
 
 class Op:
-    """kind: 'c1' | 'conv' | 'down' | 'deconv' | 'pool' | 'up'."""
+    """kind: 'c1' | 'conv' | 'down' | 'deconv' | 'pool' | 'up' | 'res' (residual add + ReLU, vnet.py:64-67: srcs = [the block's last-stage
+    value] + the names of the block's input; none = the one-channel network input)."""
 
     def __init__(self, kind, out, srcs, **kw):
         self.kind, self.out, self.srcs = kind, out, list(srcs)
@@ -40,6 +41,7 @@ class Op:
                                                     # parallel streams (they only meet again in the encoder's backward)
         self.inorm = kw.get("inorm", False)          # InstanceNorm (no affine) + ReLU after the conv: batch-of-one statistics
         self.half_pixel = kw.get("half_pixel", False)  # 'up': align_corners=False
+        self.noact = kw.get("noact", False)            # BatchNorm without an activation behind it (last stage of a residual block: a 'res' op follows)
 
 
 class Program:
@@ -60,7 +62,7 @@ def _taps(op, dims):
 def _op_sig(op):
     """What two ops must share to resolve to the same kernel launches (same instance, grid, call sequence)."""
     return (op.kind, op.ksize, op.cin, op.cout, bool(op.bn), op.head, op.combine, op.inorm, op.half_pixel, len(op.srcs),
-            None if not op.drop else (op.drop[1], op.drop[2]), op.slope)
+            None if not op.drop else (op.drop[1], op.drop[2]), op.slope, op.noact)
 
 
 def zip_branches(a_ops, b_ops):
@@ -161,6 +163,7 @@ class Saved:
         self.tables = None   # perturbed pass: branch -> value table of that decoder (trunk values overlaid)
         self.fold = {}       # perturbed pass: branch -> {trunk value name: chan_mul [B + U, C] or None}
         self.n_dec = 0       # perturbed pass: the decoders' batch size B + U
+        self.dxin = None     # backward pass: gradient of the image through block_one's residual add (fp32 [N, D*H*W]), added to dx by the first conv
 
 
 class Executor:
@@ -342,9 +345,46 @@ class Executor:
                 pre_keep[id(op_)] = keep
             yield [lambda op_=op_: make_keep(op_) for op_ in elem]        # (a step of every training-mode pass, possibly without lanes: passes driven together stay aligned)
 
+        def apply_drop(op, lz, out, n):
+            """Dropout on the OUTPUT value of `op` (training mode): the keep mask / channel multiplier its consumers apply while loading."""
+            site, p, mode = op.drop
+            if mode == "elem":
+                if drop_masks is not None:
+                    keep = drop_masks.get(site)
+                elif id(op) in pre_keep:
+                    keep = pre_keep[id(op)]
+                    assert keep.shape == out.shape
+                else:
+                    keep = L.hold_empty(out.shape, dtype=torch.uint8, device=dev)
+                    ops.keep_mask(keep, drop_seed[id(op)], p, seed_dev=rng.seed_dev)
+                if keep is not None:
+                    lz.keep, lz.keep_scale = keep, 1.0 / (1.0 - p)
+            else:
+                if drop_masks is not None:
+                    cm = drop_masks.get(site)
+                else:
+                    cm = L.hold_empty(n, op.cout, dtype=torch.float32, device=dev)
+                    ops.chan_mask(cm, drop_seed[id(op)], p, seed_dev=rng.seed_dev)
+                if cm is not None:
+                    lz.chan_mul = cm
+
         def run_op(op, V=vals, n=N):      # V / n: value table and batch size (the decoders of a perturbed pass see their own)
             nonlocal apos
             k = op.kind
+            if k == "res":
+                # out = relu(last + x), x = the block's input summed first (vnet.py:64-67); materialised: the value is a plain tensor
+                r = V[op.srcs[0]]
+                srcs = [V[s] for s in op.srcs[1:]]
+                gd = vdims[op.srcs[0]]
+                if not srcs and x.shape[1] != 1:
+                    raise ValueError("chap_amd: a residual first block needs a one-channel input (got %d)" % x.shape[1])
+                out = L.hold_empty((n,) + gd + (r.C,), dtype=dtype, device=dev)
+                ops.residual_fwd(r, srcs, out, xin=None if srcs else x.view(n, -1))
+                lz = Lazy(out)
+                if op.drop and train:
+                    apply_drop(op, lz, out, n)
+                V[op.out], vdims[op.out] = lz, gd
+                return
             if k == "pool":
                 src = V[op.srcs[0]]
                 d, h, w = vdims[op.srcs[0]]
@@ -438,30 +478,11 @@ class Executor:
                 else:
                     ops.bn_eval_affine(sd[op.bn + ".weight"], sd[op.bn + ".bias"], sd[op.bn + ".running_mean"], sd[op.bn + ".running_var"],
                                        BN_EPS, scale, shift)
-                lz = Lazy(out, scale, shift, True, op.slope)
+                lz = Lazy(out, scale, shift, not op.noact, op.slope)
             else:
                 lz = Lazy(out)
             if op.drop and train:
-                site, p, mode = op.drop
-                if mode == "elem":
-                    if drop_masks is not None:
-                        keep = drop_masks.get(site)
-                    elif id(op) in pre_keep:
-                        keep = pre_keep[id(op)]
-                        assert keep.shape == out.shape
-                    else:
-                        keep = L.hold_empty(out.shape, dtype=torch.uint8, device=dev)
-                        ops.keep_mask(keep, drop_seed[id(op)], p, seed_dev=rng.seed_dev)
-                    if keep is not None:
-                        lz.keep, lz.keep_scale = keep, 1.0 / (1.0 - p)
-                else:
-                    if drop_masks is not None:
-                        cm = drop_masks.get(site)
-                    else:
-                        cm = L.hold_empty(n, op.cout, dtype=torch.float32, device=dev)
-                        ops.chan_mask(cm, drop_seed[id(op)], p, seed_dev=rng.seed_dev)
-                    if cm is not None:
-                        lz.chan_mul = cm
+                apply_drop(op, lz, out, n)
             V[op.out] = lz
         # ---- schedule: trunk, then the decoders side by side (second decoder on a forked stream)
         for op in prog.ops:
@@ -535,6 +556,18 @@ class Executor:
             c = contrib.get(name)
             return None if not c else [(t, o) for t, o, _ in sorted(c, key=lambda e: e[2])]
 
+        def incoming3(name, C, shape):
+            """incoming(), folded to at most three contributions -- what chap_act_bwd_* and chap_residual_bwd take: the OLDEST ones (program order)
+            are summed first by chap_grad_sum, up to four at a time.  A skip feature of a residual DualDecoder3d has five: the down conv and, per
+            decoder, the block's first conv and its residual add."""
+            c = incoming(name)
+            while c and len(c) > 3:
+                k = min(4, len(c) - 2)
+                t = L.hold_empty(shape + (C,), dtype=dtype, device=dev)
+                ops.grad_sum(c[:k], t)
+                c = [(t, 0)] + c[k:]
+            return c
+
         pooled = {}         # value name -> (grad tensor, idx)
         head_g = dict(zip(prog.heads, dlogits))
         dx = None
@@ -597,6 +630,23 @@ class Executor:
                     ops.upsample2x_bwd(c[0][0], c[0][1], src.C, o, dims=dims)
                     contrib.setdefault(op.srcs[0], []).append((o, 0, okey[id(op)]))
                 return
+            if k == "res":
+                gd = S.dims[op.out]
+                v = V[op.out]
+                c = incoming3(op.out, v.C, (n,) + gd)
+                if not c:
+                    return
+                if S.tables is not None:
+                    raise NotImplementedError("chap_amd: residual blocks in a channel-perturbed pass")
+                gout = L.hold_empty((n,) + gd + (v.C,), dtype=dtype, device=dev)
+                dxin = None
+                if len(op.srcs) == 1 and need_dx:        # block_one: the image was the block's input
+                    dxin = S.dxin = L.hold_empty(n, gd[0] * gd[1] * gd[2], dtype=torch.float32, device=dev)
+                ops.residual_bwd(c, v.raw, gout, chan_mul=v.chan_mul, dxin=dxin)
+                # the gradient of relu(last + x) w.r.t. last and w.r.t. every source of x is the same tensor
+                for name in op.srcs:
+                    contrib.setdefault(name, []).append((gout, 0, okey[id(op)]))
+                return
             # ---- gradient w.r.t. the raw output of this conv
             v = None
             if op.head:
@@ -609,12 +659,12 @@ class Executor:
                 g = Lazy(g16)
                 kn_valid = op.cout
             else:
-                c = incoming(op.out)
+                v = V[op.out]
+                gd = S.dims[op.out]
+                c = incoming3(op.out, v.C, (n,) + gd)
                 pl = pooled.get(op.out)
                 if not c and pl is None:
                     return
-                v = V[op.out]
-                gd = S.dims[op.out]
                 kn_valid = 0
                 plain = (v.scale is None and not v.act and v.keep is None and v.chan_mul is None)
                 if plain and pl is None and len(c) == 1:
@@ -661,6 +711,8 @@ class Executor:
                     wp = self._pack(op, L.PACK_CONV_DGRAD, dtype, sd)
                     ops.conv_fwd([g], wp, None, S.x.shape[1], dx, grid=(n, D, H, W), in_dims=(D, H, W), ksize=3, stride=1, dims=dims,
                                  out_planar=True, out_f32=True)
+                    if S.dxin is not None:               # residual block_one: dx += the gradient through the add (the 'res' op ran before this one)
+                        ops.perturb(dx, S.dxin, dx, 1.0)
                 return
             srcs = [V[s] for s in op.srcs]
             sd_, sh_, sw_ = S.dims[op.srcs[0]]

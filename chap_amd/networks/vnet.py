@@ -7,7 +7,10 @@ hand-scheduled HIP program (chap_amd.engine) on NDHWC tensors.
     Upsampling_function    vnet.py:97-125   mode 0: ConvTranspose3d k2 s2 | mode 1: trilinear x2 (align_corners) + Conv3d 3^3; -> BN -> ReLU
     Encoder vnet.py:127-168   Decoder vnet.py:170-223 (skip ADD, Dropout3d(.5) on x5 / x9)
     DualDecoder3d vnet.py:225-238   VNet vnet.py:303-315
-Only normalization='batchnorm', has_residual=False (what net_factory_3d builds) is implemented.
+    ResidualConvBlock      vnet.py:37-67    has_residual=True (vnet.py:131, :175): the last stage has no ReLU, then ReLU(last + block input);
+                                            in encoder.block_one the one-channel image is broadcast over the 16 channels (n_channels must be 1:
+                                            the reference's conv(x) + x cannot broadcast 3 channels against 16).  Same module tree and keys.
+Only normalization='batchnorm' is implemented (net_factory_3d builds it with has_residual=False).
 """
 import torch.nn as nn
 
@@ -67,21 +70,26 @@ def _decoder(n_classes, nf, up_type):
     return dec
 
 
-def build_program(n_classes, nf, decoders, has_dropout, n_channels=1):
-    """decoders: list of (root, up_type)."""
+def build_program(n_classes, nf, decoders, has_dropout, n_channels=1, has_residual=False):
+    """decoders: list of (root, up_type).  has_residual: every block's last stage is a conv + BatchNorm without ReLU (`noact`) followed by a
+    'res' op, out = ReLU(last + block input); the Dropout3d site of x5 / x9 moves to the 'res' op."""
     ops = []
 
     def block(pre, srcs, out, n, cin, cout, first=False, combine=0, drop=None):
         cur = srcs
         for s in range(n):
-            name = out if s == n - 1 else "%s.s%d" % (out, s)
+            last = s == n - 1
+            name = (out + ".last" if has_residual else out) if last else "%s.s%d" % (out, s)
             kw = dict(w="%s.conv.%d.weight" % (pre, 3 * s), b="%s.conv.%d.bias" % (pre, 3 * s), bn="%s.conv.%d" % (pre, 3 * s + 1),
-                      slope=0.0, cin=cin if s == 0 else cout, cout=cout, drop=drop if s == n - 1 else None)
+                      slope=0.0, cin=cin if s == 0 else cout, cout=cout, drop=drop if (last and not has_residual) else None,
+                      noact=last and has_residual)
             if first and s == 0:
                 ops.append(Op("c1", name, [], **kw))
             else:
                 ops.append(Op("conv", name, cur, ksize=3, combine=combine if s == 0 else 0, **kw))
             cur = [name]
+        if has_residual:
+            ops.append(Op("res", out, cur + ([] if first else list(srcs)), cin=cout, cout=cout, drop=drop))
 
     c = n_channels
     x = None
@@ -120,8 +128,11 @@ def build_program(n_classes, nf, decoders, has_dropout, n_channels=1):
 
 
 def _check(normalization, has_residual, n_channels):
-    if normalization != "batchnorm" or has_residual:
-        raise NotImplementedError("chap_amd: only normalization='batchnorm', has_residual=False (net_factory_3d's configuration) is built")
+    if normalization != "batchnorm":
+        raise NotImplementedError("chap_amd: only normalization='batchnorm' (net_factory_3d's configuration) is built")
+    if has_residual and n_channels != 1:
+        raise ValueError("chap_amd: has_residual=True needs n_channels=1 (got %d): the reference's ResidualConvBlock adds conv(x) + x "
+                         "(vnet.py:65), which cannot broadcast %d input channels against block_one's 16" % (n_channels, n_channels))
     if not 1 <= n_channels <= 16:
         raise NotImplementedError("chap_amd: n_channels=%d (1..16: the first layer runs on the input zero-padded to 16 channels)" % n_channels)
 
@@ -139,7 +150,7 @@ class DualDecoder3d(ChapNet):
         self.decoder1 = _decoder(n_classes, n_filters, 1)
         self.decoder2 = _decoder(n_classes, n_filters, 0)
         self.encoder.has_dropout = self.decoder1.has_dropout = self.decoder2.has_dropout = has_dropout
-        self._finish_init(build_program(n_classes, n_filters, [("decoder1", 1), ("decoder2", 0)], has_dropout, n_channels))
+        self._finish_init(build_program(n_classes, n_filters, [("decoder1", 1), ("decoder2", 0)], has_dropout, n_channels, bool(has_residual)))
 
     def forward(self, input, drop_masks=None, update_stats=True, grad_buffer=None):
         out = self._run(input, drop_masks=drop_masks, update_stats=update_stats, grad_buffer=grad_buffer)
@@ -158,7 +169,7 @@ class VNet(ChapNet):
         self.encoder = _encoder(n_channels, n_filters)
         self.decoder = _decoder(n_classes, n_filters, 0)
         self.encoder.has_dropout = self.decoder.has_dropout = has_dropout
-        self._finish_init(build_program(n_classes, n_filters, [("decoder", 0)], has_dropout, n_channels))
+        self._finish_init(build_program(n_classes, n_filters, [("decoder", 0)], has_dropout, n_channels, bool(has_residual)))
 
     def forward(self, input, drop_masks=None, update_stats=True, grad_buffer=None):
         return self._run(input, drop_masks=drop_masks, update_stats=update_stats, grad_buffer=grad_buffer)[0]

@@ -247,6 +247,45 @@ def act_bwd_sums_size(c):
     return (1 + L.ACT_BWD_SLOTS) * 2 * c
 
 
+def residual_fwd(r, srcs, out, xin=None):
+    """chap_residual_fwd: out = relu(a(r) + t) with t = the block input: the sum of the lazy sources `srcs` (one or two), or xin
+    (fp32 [N, D*H*W], the one-channel image broadcast over the channels) when there are none.  r: the last stage's Lazy (act off)."""
+    p = L.ResidualParams()
+    r.fill(p.r)
+    for i, s in enumerate(srcs):
+        s.fill(p.src[i])
+    p.nsrc, p.xin, p.out = len(srcs), _p(xin), out.data_ptr()
+    p.N, p.D, p.H, p.W = r.raw.shape[:4]
+    p.dtype = dt(r.raw)
+    L.call("chap_residual_fwd", p, _stream())
+
+
+def residual_bwd(grads, out, gout, chan_mul=None, dxin=None):
+    """chap_residual_bwd: gout = (sum of up to three grads) * chan_mul * [out > 0]; grads: list of (tensor, channel offset);
+    dxin (fp32 [N, D*H*W] or None) receives the channel sum of the unrounded value."""
+    p = L.ResidualBwdParams()
+    if len(grads) > 3:
+        raise ValueError("residual_bwd: %d gradient contributions (1..3; fold the oldest with grad_sum)" % len(grads))
+    for i, (g, coff) in enumerate(grads):
+        p.g[i], p.g_ld[i], p.g_coff[i] = g.data_ptr(), g.shape[-1], coff
+    p.ng = len(grads)
+    p.out, p.chan_mul, p.gout, p.dxin = out.data_ptr(), _p(chan_mul), gout.data_ptr(), _p(dxin)
+    p.N, p.D, p.H, p.W, p.C = out.shape
+    p.dtype = dt(out)
+    L.call("chap_residual_bwd", p, _stream())
+
+
+def grad_sum(grads, out):
+    """chap_grad_sum: out [..., C] = ((g0 + g1) + g2) + g3 of two to four (tensor, channel offset) contributions, fp32 adds."""
+    p = L.GradSumParams()
+    if len(grads) > 4:
+        raise ValueError("grad_sum: %d tensors (2..4)" % len(grads))
+    for i, (g, coff) in enumerate(grads):
+        p.g[i], p.g_ld[i], p.g_coff[i] = g.data_ptr(), g.shape[-1], coff
+    p.ng, p.out, p.npix, p.C, p.dtype = len(grads), out.data_ptr(), out[..., 0].numel(), out.shape[-1], dt(out)
+    L.call("chap_grad_sum", p, _stream())
+
+
 def channel_sum(lazy, out):
     p = L.ChanSumParams()
     lazy.fill(p.r)

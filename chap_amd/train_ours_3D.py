@@ -8,7 +8,8 @@ loader with `next_into`, chap_amd.data.DeviceLoader, feeds the captured iteratio
 `args["labeled_num"]` (the LA h5 layout of test_LA.py:25-28: the first `labeled_num` cases of `train.list` are the labelled ones,
 volumes resident on the device, random crops zero-padded where a volume is smaller than the patch); else the fixed-seed synthetic
 generator.  Validation: `args["val_volumes"]`, a list of (image [w,h,d], label [w,h,d]) arrays, scored by the sliding window of
-chap_amd.test_3d_patch.var_all_case (mean foreground Dice, first decoder).  `dropout=True` is unsupported in 3D (ChapStep raises)."""
+chap_amd.test_3d_patch.var_all_case (mean foreground Dice, first decoder).  `dropout=True` is unsupported in 3D (ChapStep raises).
+`args["has_residual"]` (default False) builds the network with residual V-Net blocks (vnet.py:37-67)."""
 import csv
 import logging
 import os
@@ -18,6 +19,7 @@ import numpy as np
 import torch
 
 from .networks.net_factory_3d import net_factory_3d
+from .networks.vnet import DualDecoder3d, VNet
 from .synthetic import synthetic_batch_3d
 from .test_3d_patch import var_all_case
 from .train import DEFAULT_ARGS, ChapStep
@@ -46,7 +48,14 @@ def train(args, snapshot_path):
         device = torch.device("cuda", a["gpu"])
         torch.manual_seed(a["seed"])
         np.random.seed(a["seed"])
-        model = net_factory_3d(net_type=a["model"], in_chns=1, class_num=a["num_classes"], mode="train", device=device, args=a)
+        if a.get("has_residual", False):
+            # ResidualConvBlock nets (vnet.py:37-67): net_factory_3d keeps the reference's signature, which has no such flag, so the class is built
+            # here with the factory's train-mode arguments
+            cls = {"vnet": VNet, "dualdecoder": DualDecoder3d}.get(a["model"])
+            kw = dict(args=a) if cls is DualDecoder3d else {}
+            model = cls(n_channels=1, n_classes=a["num_classes"], normalization="batchnorm", has_dropout=True, has_residual=True, **kw).to(device) if cls else None
+        else:
+            model = net_factory_3d(net_type=a["model"], in_chns=1, class_num=a["num_classes"], mode="train", device=device, args=a)
         if model is None:
             raise ValueError("chap_amd.train_ours_3D: no 3D network named %r" % (a["model"],))
         model.train()

@@ -46,6 +46,7 @@
  *      Additive, no version change: chap_augment2d / chap_augment3d (device-resident training input, new structs only).
  *      Additive, no version change: chap_window_gather / chap_window_accumulate_heads / chap_augment3d_padded (the 3D workflow: device-side
  *      sliding-window patches, one- or two-head score accumulation, zero-padded training crops; new structs only).
+ *      Additive, no version change: chap_residual_fwd / chap_residual_bwd / chap_grad_sum (residual V-Net blocks; new structs only).
  *   9  (8 was the in-launch BatchNorm finalize, withdrawn before any release) chap_diffmask_params carries the integer count k instead of the float fraction topk: the library computed (int)(topk_f32 * (float)M),
  *      one more than the definition's max(int(topk * M), 1) in double for e.g. topk = 0.29, M = 100.  The caller computes k.
  */
@@ -578,6 +579,48 @@ typedef struct { const void* g; const float* mul; void* out; int32_t B, U, C, ld
 int chap_fold_perturbed(const chap_fold_params* p, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Residual V-Net block, ResidualConvBlock (vnet.py:37-67; chosen by has_residual at vnet.py:131 and :175): the block's last stage is
+ * Conv3d -> BatchNorm WITHOUT ReLU, then  out = ReLU(last + x)  with x the block's input (vnet.py:64-67).  Additive, no version
+ * change (new structs only).  Streaming kernels: one lane = 8 channels of one voxel, fp32 arithmetic, no atomics; all three may be
+ * called inside a group region (chap_group_begin).  C % 8 == 0, voxels * C / 8 < 2^32.
+ *
+ * chap_residual_fwd:  out = max(0, (scale * r + shift) + t)   -- out [voxels][C] dense, op dtype
+ *   r      the last conv's raw output with its BatchNorm affine; r.act must be 0
+ *   t      the block input, summed FIRST as the reference does (x5_up = x5_up + x4, vnet.py:202, before block_six reads it):
+ *          nsrc 1: a(src[0]);  nsrc 2: a(src[0]) + a(src[1])  (each with its full load transform: affine, leaky / ReLU, keep,
+ *          chan_mul);  nsrc 0: xin[n][voxel], the one-channel network input broadcast over C (encoder.block_one, vnet.py:133 with
+ *          n_channels = 1) -- exactly one of nsrc > 0 and xin != NULL. */
+typedef struct {
+    chap_src_t   r;
+    chap_src_t   src[2];  int32_t nsrc;
+    const float* xin;          /* fp32 planar [N][D*H*W] or NULL                                   */
+    void*        out;
+    int32_t      N, D, H, W, dtype;
+} chap_residual_params;
+int chap_residual_fwd(const chap_residual_params* p, void* stream);
+
+/* chap_residual_bwd:  gout = ((g[0] + g[1]) + g[2]) * chan_mul[n][c] * [out > 0]   (strictly greater: torch's ReLU gradient at 0)
+ *   g, g_ld, g_coff, ng (1..3)   gradient contributions w.r.t. the activated output, as in chap_act_bwd_params
+ *   out        the forward result;   chan_mul: [N][C] or NULL, the Dropout3d multiplier on the output (vnet.py:164-165, 218-219)
+ *   gout       [voxels][C] dtype: the gradient of the last stage's BatchNorm output AND of every block-input source
+ *   dxin       fp32 planar [N][D*H*W] or NULL: sum_c of the UNROUNDED fp32 value (the gradient of the broadcast input): a lane sums
+ *              its 8 channels in ascending order, then a fixed xor butterfly over the C/8 lanes of the voxel (C/8 a power of two
+ *              <= 64): bitwise reproducible. */
+typedef struct {
+    const void* g[3];  int32_t g_ld[3];  int32_t g_coff[3];  int32_t ng;
+    const void* out;   const float* chan_mul;
+    void*  gout;       float* dxin;
+    int32_t N, D, H, W, C, dtype;
+} chap_residual_bwd_params;
+int chap_residual_bwd(const chap_residual_bwd_params* p, void* stream);
+
+/* chap_grad_sum:  out = ((g[0] + g[1]) + g[2]) + g[3]  for ng in 2..4 same-grid tensors (ptr, ld, coff), fp32 adds, stored in the op
+ * dtype, out [pixels][C] dense.  chap_act_bwd_* and chap_residual_bwd take three contributions; a skip feature of a residual
+ * DualDecoder3d has five (the down conv and, per decoder, the block's first conv and its residual add: vnet.py:202-216 with :64-67). */
+typedef struct { const void* g[4]; int32_t g_ld[4]; int32_t g_coff[4]; int32_t ng; void* out; int64_t npix; int32_t C, dtype; } chap_grad_sum_params;
+int chap_grad_sum(const chap_grad_sum_params* p, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * grad.GradSim (ABSENT from the reference; call sites train_ours_2D.py:288,297,360,365; DESIGN.md "N1"): per OUTPUT
  * channel c of a conv kernel, the cosine similarity of the labeled-loss and the unlabeled-loss gradients
  *     sim[c] = <gl[c,:], gu[c,:]> / (||gl[c,:]|| * ||gu[c,:]|| + 1e-12),   rows of K = Cin * taps contiguous floats
@@ -597,7 +640,7 @@ int chap_grad_sim(const chap_gradsim_params* p, void* stream);
  *
  * Between begin and end the entry points of the networks' forward / backward path (chap_conv_fwd, chap_conv_c1_*, chap_wgrad,
  * chap_bn_finalize, chap_bn_eval_affine, chap_act_bwd_*, chap_act_pool2, chap_upsample2x*, chap_planar_to_cl, chap_cl_to_planar,
- * chap_channel_sum, chap_keep_mask, chap_chan_mask, chap_fold_perturbed) check their arguments and RECORD their launches instead
+ * chap_channel_sum, chap_keep_mask, chap_chan_mask, chap_fold_perturbed, chap_residual_fwd, chap_residual_bwd, chap_grad_sum) check their arguments and RECORD their launches instead
  * of issuing them; chap_group_end issues, for j = 0, 1, ..., the j-th recorded launch of every lane -- as ONE grid (gridDim.z = lanes,
  * up to 4) when they resolved to the same kernel instance and launch geometry, else one after the other in lane order.  Every block
  * does exactly the work it would do in a launch of its own (same tiles, same reduction slots): results are bit-identical to the
