@@ -46,6 +46,8 @@ static inline int conv_make_plan(const chap_conv_params* p, conv_plan* q) {
     CHAP_CHECK_ARG(p->nsrc == 1 || p->nsrc == 2, "chap_conv_fwd: nsrc=%d", p->nsrc);
     for (int i = 0; i < p->nsrc; ++i) { int r = conv_check_src(p->src[i], "chap_conv_fwd src"); if (r) return r; }
     CHAP_CHECK_ARG(p->combine == 0 || (p->nsrc == 1 || p->src[0].C == p->src[1].C), "chap_conv_fwd: add-combine needs equal C");
+    // (the staging of an add-combined pair applies keep mask and channel multipliers of the FIRST source only: conv_kernel.h halo_commit_impl)
+    if (p->combine == 1 && p->nsrc == 2 && (p->src[1].keep || p->src[1].chan_mul)) { chap_set_error("chap_conv_fwd: add-combine takes a keep mask / channel multipliers on the first source only"); return CHAP_EUNSUPPORTED; }
     CHAP_CHECK_ARG(p->N > 0 && p->D > 0 && p->H > 0 && p->W > 0, "chap_conv_fwd: empty grid");
     CHAP_CHECK_ARG(p->dims == 2 || p->dims == 3, "chap_conv_fwd: dims=%d", p->dims);
     CHAP_CHECK_ARG(p->wpacked && p->out && p->Cout > 0, "chap_conv_fwd: null weights/out");

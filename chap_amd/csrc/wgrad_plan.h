@@ -15,6 +15,8 @@ static inline int wg_make_plan(const chap_wgrad_params* p, wg_plan* q) {
     q->Ca = p->combine == 0 ? p->a[0].C + (p->na > 1 ? p->a[1].C : 0) : p->a[0].C;
     q->Cb = p->b.C;
     CHAP_CHECK_ARG(q->Ca % 16 == 0 && q->Cb % 8 == 0, "chap_wgrad: Ca=%d must be a multiple of 16, Cb=%d of 8", q->Ca, q->Cb);
+    // (the staging of an add-combined pair applies keep mask and channel multipliers of the FIRST source only: conv_kernel.h halo_commit_impl)
+    if (p->combine == 1 && p->na == 2 && (p->a[1].keep || p->a[1].chan_mul)) { chap_set_error("chap_wgrad: add-combine takes a keep mask / channel multipliers on the first source only"); return CHAP_EUNSUPPORTED; }
     q->KC = (q->Ca >= 32 && q->Ca % 32 == 0) ? 32 : 16;
     if (p->dtype == CHAP_F32 && p->ksize == 2) q->KC = 16;      // fp32 k2 s2 halos: two buffers of 32 channels exceed the 160 KiB LDS
     // 3D 3x3x3, bf16: 4 x 4 x 16 bricks with 16-channel A chunks (the 1 x 4 x 16 slab stages 5.1 A-pixels per output pixel and pays a

@@ -88,6 +88,16 @@ def zip_branches(a_ops, b_ops):
     return out
 
 
+def fold_oldest_first(c, fold, limit=3, width=4):
+    """A list of more than `limit` summands (program order) -> at most `limit`: the OLDEST ones are summed first, up to `width` at a time, by
+    fold(group) -> summand, which takes their place at the front.  The order is part of the result: a floating-point sum is not associative, and
+    eager, captured and data-parallel runs must agree bit for bit (tests/test_vnet_residual_cpu.py pins it)."""
+    while c and len(c) > limit:
+        k = min(width, len(c) - (limit - 1))
+        c = [fold(c[:k])] + c[k:]
+    return c
+
+
 def drive(gen, stream):
     """Run a step generator (Executor.forward_steps / backward_steps): the lanes of a step -- the same-shaped ops of the two decoders --
     are enqueued inside ONE grouped launch region (their kernels become one grid), a single lane directly.  Returns the generator's
@@ -560,13 +570,11 @@ class Executor:
             """incoming(), folded to at most three contributions -- what chap_act_bwd_* and chap_residual_bwd take: the OLDEST ones (program order)
             are summed first by chap_grad_sum, up to four at a time.  A skip feature of a residual DualDecoder3d has five: the down conv and, per
             decoder, the block's first conv and its residual add."""
-            c = incoming(name)
-            while c and len(c) > 3:
-                k = min(4, len(c) - 2)
+            def fold(group):
                 t = L.hold_empty(shape + (C,), dtype=dtype, device=dev)
-                ops.grad_sum(c[:k], t)
-                c = [(t, 0)] + c[k:]
-            return c
+                ops.grad_sum(group, t)
+                return (t, 0)
+            return fold_oldest_first(incoming(name), fold)
 
         pooled = {}         # value name -> (grad tensor, idx)
         head_g = dict(zip(prog.heads, dlogits))

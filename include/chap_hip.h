@@ -90,7 +90,8 @@ typedef struct {
  * Implicit-GEMM convolution, forward.  Replaces nn.Conv2d/Conv3d (unet.py:50,54,86,168;
  * vnet.py:19,76,106,189), nn.ConvTranspose2d/3d (unet.py:90; vnet.py:103) and -- with packed
  * weights of kind *_DGRAD -- their input-gradient.  Up to two inputs, concatenated
- * (torch.cat, unet.py:97) or added (skip add, vnet.py:202).
+ * (torch.cat, unet.py:97) or added (skip add, vnet.py:202; an added pair takes a keep mask / channel multipliers on
+ * src[0] only: CHAP_EUNSUPPORTED on src[1], in chap_conv_fwd and chap_wgrad).
  *   geometry      kernel k^3 (2D: 1 x k x k), stride s, pad (k-s)/2 ... supported (k,s):
  *                 (3,1) "same", (1,1), (2,2) down-sampling.
  *   out_mode 1    depth-to-space: logical output channel n' = sub*Cn + c is stored at fine pixel

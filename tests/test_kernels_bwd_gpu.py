@@ -393,6 +393,34 @@ def test_wgrad_conv3d_ragged(dtype, shape, cin, cout, add2, brick, monkeypatch):
     kr.check("db", db, rw["db"], kr.wgrad_bound(rw, which="db"))
 
 
+@pytest.mark.parametrize("kind", ["plain", "chan_mul", "add", "add_second"])
+@pytest.mark.parametrize("dtype,brick", [(torch.float32, False), (torch.bfloat16, False), (torch.bfloat16, True)])      # (brick tiles are bf16 only)
+@pytest.mark.parametrize("shape,cin,cout", [((2, 10, 14, 14), 32, 32), ((1, 9, 13, 20), 16, 16), ((2, 5, 7, 7), 64, 128)])
+def test_wgrad_conv3d_residual_sources(dtype, shape, cin, cout, brick, kind, monkeypatch):
+    """test_wgrad_conv3d_ragged's shapes and `brick` switch (bricks with 16- and 32-wide B tiles, slabs in both types) with the A operands only a
+    residual net gives the weight gradient (tests/test_kernels_gpu.py::residual_sources: no affine and no activation -- the kernels' plainA
+    branch --, the same behind Dropout3d multipliers, the skip add of such a source and a lazy BatchNorm + ReLU one): dW accumulated into an
+    existing tensor and db, per element against the fp64 restatement."""
+    from tests import kernel_ref as kr
+    from tests.test_kernels_gpu import residual_sources
+    monkeypatch.setenv("CHAP_WGRAD_BRICK", "1" if brick else "0")
+    g = torch.Generator().manual_seed(sum(map(ord, kind)) + cin)
+    N, D, H, W = shape
+    srcs, combine, parts = residual_sources(kind, dtype, shape, cin, g)
+    gy = rq(torch.randn(N, cout, D, H, W, generator=g), dtype)
+    dw = torch.full((cout, cin, 3, 3, 3), 0.25, device=DEV)
+    db = torch.zeros(cout, device=DEV)
+    ops.wgrad(srcs, ops.Lazy(cl(gy, dtype)), dw, (1, 27, cin * 27), grid=(N, D, H, W), in_dims=(D, H, W), ksize=3, stride=1, dims=3, combine=combine, db=db)
+    torch.cuda.synchronize()
+    av, flip = kr.mfma_operand(*(kr.add_f32(parts) if combine else parts[0]), dtype)
+    rw = kr.wgrad_ref(av, gy.double(), ksize=3, stride=1, flipA=flip)
+    prior = torch.full((27, cin, cout), 0.25, dtype=torch.float64)
+    st = (1, 27, cin * 27)
+    w = [kr.check("dW", dw, kr.to_layout(rw["dw"] + prior, st, dw.shape), kr.to_layout(kr.wgrad_bound(rw, prior), st, dw.shape)),
+         kr.check("db", db, rw["db"], kr.wgrad_bound(rw, which="db"))]
+    print("wgrad %s %s brick=%s %s: worst err/bound %s" % (shape, dtype, brick, kind, " ".join("%.3f" % v for v in w)))
+
+
 @pytest.mark.parametrize("mr", [2, 1])
 @pytest.mark.parametrize("cins,cout,hw,keep", [([16], 16, (40, 52), True), ([16, 16], 16, (37, 50), False), ([32], 32, (24, 40), False), ([32, 32], 32, (19, 33), True),
                                                ([16], 4, (33, 47), False)])
@@ -456,10 +484,13 @@ def _act_matrix_case(case, C):
         return (2, 1, 2 * -(-(1100 * ppb) // (4 * W)), W), 0, True, 1, False, False
     if case == "3d_bn2":                                   # fixed affine, dgamma / dbeta from the same reduction, Dropout3d multipliers
         return (2, 3, 5, 12), 3, False, 2, False, True
+    if case in ("3d_noact_bn1", "3d_noact_bn2"):           # a residual block's last stage: BatchNorm with NO activation behind it (act=False, no dropout);
+        bn = int(case[-1])                                 # gradient sources for C = 16 .. 256 (the second one at an offset): bn 1: 3, 1, 2, 3, 1; bn 2: 1, 2, 3, 1, 2
+        return (2, 3, 5, 12), 1 + (C.bit_length() - 4 + bn) % 3, False, bn, False, False
     return (1, 4, 6, 7), 1, False, 0, False, True          # "3d_bn0"
 
 
-@pytest.mark.parametrize("case", ["2d_small", "2d_capped", "3d_bn2", "3d_bn0"])
+@pytest.mark.parametrize("case", ["2d_small", "2d_capped", "3d_bn2", "3d_bn0", "3d_noact_bn1", "3d_noact_bn2"])
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("C", [8, 16, 32, 64, 128, 256])
 def test_act_bwd_matrix(C, dtype, case):
@@ -469,6 +500,7 @@ def test_act_bwd_matrix(C, dtype, case):
     (tests/kernel_ref.py), and bit for bit on a second launch."""
     from tests import kernel_ref as kr
     (N, D, H, W), ng, pool, bn, with_keep, with_cm = _act_matrix_case(case, C)
+    act = "noact" not in case
     g = torch.Generator().manual_seed(70 + C)
     sp = (H, W) if D == 1 else (D, H, W)
     raw = rq(torch.randn(N, C, *sp, generator=g) * 1.5 + 0.3, dtype)
@@ -484,9 +516,9 @@ def test_act_bwd_matrix(C, dtype, case):
     gp = rq(torch.randn(N, C, H // 2, W // 2, generator=g), dtype) if pool else None
     idx = torch.randint(0, 4, (N, C, H // 2, W // 2), generator=g).to(torch.uint8) if pool else None
     cnt = raw[:, 0].numel()
-    ref = kr.act_bwd_ref(raw, grads, scale=scale, shift=shift, act=True, slope=0.01, keep=keep, keep_scale=1.25, chan_mul=cm,
+    ref = kr.act_bwd_ref(raw, grads, scale=scale, shift=shift, act=act, slope=0.01, keep=keep, keep_scale=1.25, chan_mul=cm,
                          g_pool=gp, pool_idx=idx, bn_mode=bn, mean=mean if bn else None, invstd=invstd, gamma_=gamma, count=cnt)
-    lz = ops.Lazy(cl(raw, dtype), scale.to(DEV), shift.to(DEV), True, 0.01, keep=None if keep is None else cl(keep, torch.uint8),
+    lz = ops.Lazy(cl(raw, dtype), scale.to(DEV), shift.to(DEV), act, 0.01, keep=None if keep is None else cl(keep, torch.uint8),
                   keep_scale=1.25, chan_mul=None if cm is None else cm.to(DEV))
     glist = []
     for i, gr in enumerate(grads):                         # the second source sits inside a wider buffer (ld = 2C, coff = C)

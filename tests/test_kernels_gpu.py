@@ -428,6 +428,77 @@ def test_conv3d_bricks_ragged(dtype, shape, c, add2):
     kr.check("stats Q", ops.stats_totals(stats, c)[1], s2, b2)
 
 
+def residual_sources(kind, dtype, shape, c, g):
+    """The sources a residual V-Net block's output becomes (csrc/residual.hip writes a plain tensor; its consumers see a Lazy without
+    scale / shift and without an activation), as (Lazies, combine, [(v, dv), ...] of kernel_ref.lazy_f32):
+      plain      the block output alone: the conv / wgrad kernels' `plain` staging branch
+      chan_mul   the same behind Dropout3d: per-sample channel multipliers and nothing else (identity affine, slope 1 in the staging)
+      add        the decoder's skip add: a chan_mul source plus a lazy BatchNorm + ReLU source (the up conv).  The multipliers sit on the FIRST source: the
+                 staging of an add-combined pair applies those of the first source only, and the planners refuse them on the second
+                 (tests/test_launch_plan_cpu.py); the plain block output as the SECOND operand, next to the up conv, is `add_second`"""
+    N, D, H, W = shape
+    x = rq(torch.randn(N, c, D, H, W, generator=g), dtype)
+    cm = (torch.rand(N, c, generator=g) > 0.3).float() * 2.0
+    if kind == "plain":
+        return [ops.Lazy(cl(x, dtype))], 0, [kr.lazy_f32(x)]
+    res = ops.Lazy(cl(x, dtype), chan_mul=cm.to(DEV))
+    if kind == "chan_mul":
+        return [res], 0, [kr.lazy_f32(x, chan_mul=cm)]
+    assert kind in ("add", "add_second")
+    u = rq(torch.randn(N, c, D, H, W, generator=g), dtype)
+    sc, sh = torch.rand(c, generator=g) + 0.5, torch.randn(c, generator=g) * 0.2
+    up = ops.Lazy(cl(u, dtype), sc.to(DEV), sh.to(DEV), True, 0.0)
+    upv = kr.lazy_f32(u, scale=sc, shift=sh, act=True, slope=0.0)
+    if kind == "add_second":                                 # the order the V-Net decoder passes: srcs = [up, skip]
+        return [up, ops.Lazy(cl(x, dtype))], 1, [upv, kr.lazy_f32(x)]
+    return [res, up], 1, [kr.lazy_f32(x, chan_mul=cm), upv]
+
+
+# route: (dtype, shape, channels, knobs).  The routes were read off the host-only planner (conv_plan.h through the probe of tests/test_launch_plan_cpu.py); an
+# add-combined launch never takes the K-parallel kernel (conv_make_plan) and runs on the slabs with NT = 4 there.
+CONV3D_ROUTES = {
+    "slab16": (torch.bfloat16, (2, 12, 18, 30), 16, {}),        # 60 bricks < 64: 1 x 4 x 16 slabs, NT1 MR1, one chunk
+    "brick16": (torch.bfloat16, (2, 13, 18, 30), 16, {}),       # 80 bricks: z-per-wave bricks NT1 MR4 (level 0 of the 3D step)
+    "brick32": (torch.bfloat16, (2, 15, 22, 34), 32, {}),       # 144 bricks: bricks NT2 MR4, two chunks (level 1 at 112 x 112 x 80)
+    "brick64": (torch.bfloat16, (3, 10, 14, 14), 64, {"CHAP_CONV_KPAR": "0", "CHAP_CONV_MR": "4", "CHAP_CONV_NT": "2"}),      # bricks NT2 MR4, four chunks (level 2 at 112 x 112 x 80: 196 bricks), forced
+    "slab64": (torch.bfloat16, (3, 10, 14, 14), 64, {"CHAP_CONV_KPAR": "0"}),      # slabs NT4 MR1, four chunks, staged weights
+    "kpar128": (torch.bfloat16, (2, 10, 14, 14), 128, {"CHAP_CONV_KPAR": "1"}),    # K-parallel, cpar 4, two rounds
+    "slab16_f32": (torch.float32, (2, 12, 18, 30), 16, {}),
+    "slab64_f32": (torch.float32, (3, 10, 14, 14), 64, {}),
+}
+
+
+RESIDUAL_KINDS = ["plain", "chan_mul", "add", "add_second"]
+
+
+@pytest.mark.parametrize("kind", RESIDUAL_KINDS)
+@pytest.mark.parametrize("route", list(CONV3D_ROUTES))
+def test_conv3d_residual_sources(route, kind, monkeypatch):
+    """3x3x3 forward conv with bias and BatchNorm statistics on the sources only a residual net gives it (residual_sources), on every route of
+    the 3D step -- per element against the fp64 restatement.  Ragged grids; the outputs start as NaN."""
+    dtype, shape, c, knobs = CONV3D_ROUTES[route]
+    for k, v in knobs.items():
+        monkeypatch.setenv(k, v)
+    g = torch.Generator().manual_seed(sum(map(ord, route + kind)))
+    N, D, H, W = shape
+    srcs, combine, parts = residual_sources(kind, dtype, shape, c, g)
+    w = torch.randn(c, c, 3, 3, 3, generator=g) / (c * 27) ** 0.5
+    b = torch.randn(c, generator=g) * 0.1
+    cshift = torch.randn(c, generator=g) * 0.1
+    wp = ops.pack_weights(w.to(DEV), L.PACK_CONV_FWD, dtype, c, c, 27)
+    out = torch.full((N, D, H, W, c), float("nan"), device=DEV, dtype=dtype)
+    stats = ops.stats_buffer(c, DEV)
+    ops.conv_fwd(srcs, wp, b.to(DEV), c, out, grid=(N, D, H, W), in_dims=(D, H, W), ksize=3, stride=1, dims=3, combine=combine, stats=stats,
+                 stats_shift=cshift.to(DEV))
+    torch.cuda.synchronize()
+    av, flip = kr.mfma_operand(*(kr.add_f32(parts) if combine else parts[0]), dtype)
+    r = kr.conv_ref(kr.PACK_CONV_FWD, av, kr.weight_operand(w, dtype), b, flip=flip)
+    (s1, b1), (s2, b2) = kr.stats_ref(r, cshift)
+    st = ops.stats_totals(stats, c)
+    worst = [kr.check("out", uncl(out), r["y"], kr.conv_bound(r, dtype)), kr.check("stats S", st[0], s1, b1), kr.check("stats Q", st[1], s2, b2)]
+    print("conv3d %s %s: worst err/bound %s" % (route, kind, " ".join("%.3f" % v for v in worst)))
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("N,hw,cin,cout", [(4, (250, 254), 16, 16), (12, (62, 66), 64, 64), (12, (30, 34), 128, 128), (6, (126, 130), 32, 16)])
 def test_conv3x3_2d_bench_shapes_ragged(dtype, N, hw, cin, cout):

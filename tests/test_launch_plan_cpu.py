@@ -59,6 +59,8 @@ int main() {
             const int C0 = geti(m, "C0"), C1 = geti(m, "C1");
             p.src[0] = make_src(C0, geti(m, "ld0", C0), 0, geti(m, "keep0"));
             p.src[1] = make_src(C1, C1, 0, geti(m, "keep1"));
+            if (geti(m, "cm0")) p.src[0].chan_mul = (const float*)dummy;
+            if (geti(m, "cm1")) p.src[1].chan_mul = (const float*)dummy;
             p.N = geti(m, "N"); p.D = geti(m, "D", 1); p.H = geti(m, "H"); p.W = geti(m, "W");
             p.ksize = geti(m, "k"); p.stride = st; p.dims = dims;
             p.ID = p.D * sd; p.IH = p.H * st; p.IW = p.W * st;
@@ -77,7 +79,9 @@ int main() {
             memset(&p, 0, sizeof(p));
             p.na = geti(m, "na", 1); p.combine = geti(m, "combine");
             const int C0 = geti(m, "C0"), C1 = geti(m, "C1"), Cb = geti(m, "Cb");
-            p.a[0] = make_src(C0, C0, 0, 0); p.a[1] = make_src(C1, C1, 0, 0); p.b = make_src(Cb, Cb, 0, 0);
+            p.a[0] = make_src(C0, C0, 0, geti(m, "keep0")); p.a[1] = make_src(C1, C1, 0, geti(m, "keep1")); p.b = make_src(Cb, Cb, 0, 0);
+            if (geti(m, "cm0")) p.a[0].chan_mul = (const float*)dummy;
+            if (geti(m, "cm1")) p.a[1].chan_mul = (const float*)dummy;
             p.N = geti(m, "N"); p.D = geti(m, "D", 1); p.H = geti(m, "H"); p.W = geti(m, "W");
             p.ksize = geti(m, "k"); p.stride = st; p.dims = dims;
             p.ID = p.D * sd; p.IH = p.H * st; p.IW = p.W * st;
@@ -310,6 +314,57 @@ def test_workspace_is_sized_for_the_b_tile_the_dispatch_instantiates(bench_layer
         assert plan["bn"] == want["bn"] and grid[2] == -(-plan["Cb"] // plan["bn"]), (r["shape"], plan)
         # nsplit slabs of taps x Ca x Cb floats + nsplit bias-gradient rows: what the kernel's grid.x blocks write and the reduction reads
         assert plan["bytes"] == grid[0] * (plan["taps"] * plan["Ca"] * plan["Cb"] + plan["Cb"]) * 4, (r["shape"], plan)
+
+
+# ---- add-combine: dropout on the first source only --------------------------------------------------------------------------------------
+def test_add_combine_refuses_dropout_on_the_second_source(probe):
+    """The staging of an add-combined pair (conv_kernel.h halo_commit_impl, shared by the weight gradient) applies the keep mask and the channel
+    multipliers of the FIRST source; on the second they used to be ignored without a word.  The nets never ask for it (2D additive skips pass
+    [skip, up], the V-Net [up, skip] with dropout-free skips); now it is an error."""
+    conv = "conv dims=3 k=3 s=1 N=2 D=10 H=14 W=14 Cout=64 C0=64 C1=64 nsrc=2 combine=1"
+    conv2 = "conv dims=2 k=3 s=1 N=2 H=32 W=32 Cout=64 C0=64 C1=64 nsrc=2 combine=1"
+    wg = "wgrad dims=3 k=3 s=1 N=2 D=10 H=14 W=14 C0=64 C1=64 na=2 combine=1 Cb=64"
+    wg2 = "wgrad dims=2 k=3 s=1 N=2 H=32 W=32 C0=64 C1=64 na=2 combine=1 Cb=64"
+    r = probe([conv, conv + " cm0=1", conv2 + " keep0=1", wg + " cm0=1", wg2 + " keep0=1", conv + " cm1=1", conv2 + " keep1=1", wg + " cm1=1", wg2 + " keep1=1",
+               conv.replace("combine=1", "combine=0") + " cm1=1", wg.replace("combine=1", "combine=0") + " cm1=1"])
+    assert [x["rc"] for x in r[:5]] == [0] * 5
+    assert r[5] == r[6] == dict(rc=EUNSUPPORTED, error="chap_conv_fwd: add-combine takes a keep mask / channel multipliers on the first source only")
+    assert r[7] == r[8] == dict(rc=EUNSUPPORTED, error="chap_wgrad: add-combine takes a keep mask / channel multipliers on the first source only")
+    assert r[9]["rc"] == 0 and r[10]["rc"] == 0             # concatenated sources carry their own
+
+
+# ---- the shapes the residual-path GPU tests chose on the CPU -------------------------------------------------------------------------------
+def test_residual_source_cases_reach_the_routes_they_name(probe):
+    """tests/test_kernels_gpu.py::test_conv3d_residual_sources names a route per case and tests/test_step_launches_gpu.py's residual step a
+    route table: both are plans, so they are checked here (under the knobs the GPU test sets)."""
+    import torch
+    from tests.test_kernels_gpu import CONV3D_ROUTES
+    from tests.test_step_launches_gpu import RESIDUAL_SP
+    want = {"slab16": ("generic", 1, 1, 1), "brick16": ("generic", 1, 4, 1), "brick32": ("generic", 2, 4, 2), "brick64": ("generic", 2, 4, 4),
+            "slab64": ("generic", 4, 1, 4), "kpar128": ("kpar", 2, 1, 8), "slab16_f32": ("generic", 1, 1, 1), "slab64_f32": ("generic", 4, 1, 4)}
+    assert set(want) == set(CONV3D_ROUTES)
+    for route, (dtype, (N, D, H, W), c, knobs) in CONV3D_ROUTES.items():
+        base = "conv dims=3 k=3 s=1 N=%d D=%d H=%d W=%d Cout=%d C0=%d stats=1 dtype=%d" % (N, D, H, W, c, c, BF16 if dtype == torch.bfloat16 else F32)
+        pre = ["setenv " + " ".join("%s=%s" % kv for kv in knobs.items())] if knobs else []
+        one, add = probe(pre + [base + " cm0=1", base + " C1=%d nsrc=2 combine=1 cm0=1" % c])
+        assert (one["route"], one["NT"], one["MR"], one["nchunks"]) == want[route], (route, one)
+        # an add-combined launch never takes the K-parallel kernel: slabs with NT = 4 there; everywhere else the route of the single source
+        assert (add["route"], add["NT"], add["MR"]) == (("generic", 4, 1) if route == "kpar128" else want[route][:3]), (route, add)
+    # the residual step's shape: conv bricks and 16-wide weight-gradient bricks at level 0, 32-wide weight-gradient bricks and conv slabs at level 1,
+    # the K-parallel route and weight-gradient slabs from level 2 down, the head; the next smaller shape loses the 32-wide bricks
+    def level(sp, l, what):
+        d, h, w = (x >> l for x in sp)
+        c = 16 << l
+        return "%s dims=3 k=3 s=1 N=2 D=%d H=%d W=%d C0=%d %s=%d" % (what, d, h, w, c, "Cout" if what == "conv" else "Cb", c)
+    sp = RESIDUAL_SP
+    assert all(x % 16 == 0 for x in sp)
+    r = probe([level(sp, l, what) for l in range(5) for what in ("conv", "wgrad")] + ["conv dims=3 k=1 s=1 N=2 D=%d H=%d W=%d Cout=2 C0=16 planar=1 f32out=1" % sp])
+    convs, wgs = r[0:10:2], r[1:10:2]
+    assert [(x["route"], x["NT"], x["MR"]) for x in convs] == [("generic", 1, 4), ("generic", 2, 1), ("kpar", 2, 1), ("kpar", 2, 1), ("kpar", 2, 1)]
+    assert [(x["brick"], x["bn"]) for x in wgs] == [(1, 16), (1, 32), (0, 32), (0, 32), (0, 32)]
+    assert r[10]["route"] == "head"
+    smaller = (16, 16, 32)
+    assert probe([level(smaller, 1, "wgrad")])[0]["brick"] == 0
 
 
 # ---- invalid params ---------------------------------------------------------------------------------------------------------------------

@@ -7,8 +7,9 @@ dtype) the wrapper synchronises, snapshots what the call accumulates into, launc
 against the fp64 restatement with the per-element bound.  The loss, VAT / BCP, RNG, mask and optimizer launches are checked the same way
 (exactly where the result is a label, a mask or a draw; largest_cc through scipy on the host), and so are bn_finalize (from the slots the conv
 just wrote, with the running statistics snapshotted), the first conv's backward, the channel sums, the layout copies and the channel-drop kernels:
-no entry point a step calls is left without a restatement.  Run with -s for one line per signature
-(worst err / bound; 0.000 for an exact comparison)."""
+no entry point a step calls is left without a restatement.  test_every_launch_of_one_residual_step does the same for the residual 3D net
+(has_residual=True: residual_fwd / residual_bwd / grad_sum, dx += dxin), at a shape chosen with the host-only launch planner.  Run with -s for one
+line per signature (worst err / bound; 0.000 for an exact comparison)."""
 import random
 
 import numpy as np
@@ -74,6 +75,28 @@ class Checker:
     def __init__(self, weights, dtype):
         self.weights, self.dtype = weights, dtype
         self.recorded, self.checked, self.lines, self.called, self.deferred = set(), set(), [], set(), []
+        self.cm_of, self.cm_matched = {}, 0
+
+    # ---- wiring ACROSS launches, on every call (not only the first of a signature): the Dropout3d multipliers the forward consumers applied to a
+    # stored tensor are the ones chap_residual_bwd gets for it (a restatement from the call's own arguments cannot see a multiplier left out)
+    def note(self, name, a, k):
+        ptr = lambda t: None if t is None else t.data_ptr()
+        if name == "residual_bwd":
+            q = self._args(name, a, k)
+            key = (q["out"].data_ptr(), 0, q["out"].shape[-1])
+            if key in self.cm_of:
+                assert self.cm_of[key] == ptr(q["chan_mul"]), "residual_bwd: chan_mul is not the one the forward consumers of this output applied"
+                self.cm_matched += q["chan_mul"] is not None
+            return
+
+        def walk(v):
+            if isinstance(v, ops.Lazy):
+                self.cm_of[(v.raw.data_ptr(), v.coff, v.C)] = ptr(v.chan_mul)
+            elif isinstance(v, (list, tuple)):
+                for x in v:
+                    walk(x)
+        walk(a)
+        walk(list(k.values()))
 
     def report(self, key, worst):
         self.checked.add(key)
@@ -275,7 +298,10 @@ class Checker:
 
     def perturb(self, f, *a, **k):
         q = self._args("perturb", a, k)
-        ref, b = kr.perturb_ref(q["x"], q["d"], q["alpha"], q["mask"], q["sign"])
+        d = q["d"]
+        if d.shape != q["x"].shape and d.numel() == q["x"].numel():      # dx [N, 1, D, H, W] += dxin [N, D*H*W] (the residual first block): the kernel is flat
+            d = d.reshape(q["x"].shape)
+        ref, b = kr.perturb_ref(q["x"], d, q["alpha"], q["mask"], q["sign"])      # before the launch: out may BE x
         f(*a, **k)
         torch.cuda.synchronize()
         return [kr.check("perturb", q["out"].reshape(ref.shape), ref, b)]
@@ -378,6 +404,49 @@ class Checker:
         f(*a, **k)
         torch.cuda.synchronize()
         return [kr.check("grad_sim", q["score"], ref, b, "c")]
+
+    # ---- residual blocks (csrc/residual.hip): the add + ReLU, its backward with the image's gradient, the fold of more than three contributions.
+    # Chain lengths as in tests/test_residual_kernels_gpu.py: r + (src0 + src1); ((g0 + g1) + g2) and the multiplier; C for dxin's channel sum.
+    def residual_fwd(self, f, r, srcs, out, xin=None):
+        f(r, srcs, out, xin=xin)
+        torch.cuda.synchronize()
+        parts = [lazy_nc(r, 3)] + [lazy_nc(s, 3) for s in srcs]
+        if not srcs:                                        # block_one: the one-channel image, broadcast over the channels
+            n, d, h, w = out.shape[:4]
+            xi = xin.double().reshape(n, 1, d, h, w).expand_as(parts[0][0])
+            parts.append((xi, torch.zeros_like(xi)))
+        pre = sum(p[0] for p in parts)
+        ref = pre.clamp_min(0)                              # ReLU is 1-Lipschitz: the bound of the sum holds behind it
+        bnd = kr.bound(ref, sabs=sum(p[0].abs() for p in parts), chain=len(parts), flip=sum(p[1] for p in parts), store=out.dtype)
+        return [kr.check("residual_fwd out", nc(out, 3), ref, bnd)]
+
+    def residual_bwd(self, f, grads, out, gout, chan_mul=None, dxin=None):
+        f(grads, out, gout, chan_mul=chan_mul, dxin=dxin)
+        torch.cuda.synchronize()
+        C = out.shape[-1]
+        gs = [nc(t[..., c0:c0 + C], 3).double() for t, c0 in grads]
+        o = nc(out, 3).double()
+        fac = (o > 0).double()
+        if chan_mul is not None:
+            fac = fac * kr._bcast(chan_mul, o, per_sample=True)
+        ref, sabs = sum(gs) * fac, sum(t.abs() for t in gs) * fac
+        got = nc(gout, 3)
+        worst = [kr.check("residual_bwd gout", got, ref, kr.bound(ref, sabs=sabs, chain=len(gs) + 1, store=gout.dtype))]
+        assert bool((got[o == 0] == 0).all())               # strictly-greater test: exact zeros where out == 0
+        if dxin is not None:                                # the channel sum of the UNROUNDED values (each within its bound without the store term)
+            e = kr.bound(ref, sabs=sabs, chain=len(gs) + 1)
+            dref = ref.sum(1)
+            dbnd = kr.bound(dref, sabs=ref.abs().sum(1), chain=C, extra=e.sum(1), store=torch.float32)
+            worst.append(kr.check("residual_bwd dxin", dxin.reshape(dref.shape), dref, dbnd, "ndhw"))
+        return worst
+
+    def grad_sum(self, f, grads, out):
+        f(grads, out)
+        torch.cuda.synchronize()
+        C = out.shape[-1]
+        gs = [nc(t[..., c0:c0 + C], 3).double() for t, c0 in grads]
+        ref = sum(gs)
+        return [kr.check("grad_sum", nc(out, 3), ref, kr.bound(ref, sabs=sum(t.abs() for t in gs), chain=len(gs), store=out.dtype))]
 
     # ---- BatchNorm finalize / eval affine, the first conv's backward, channel sums, layout copies, the channel-drop kernels
     def bn_finalize(self, f, stats, gamma, beta, running_mean, running_var, nbt, count, eps, momentum, scale, shift, mean=None, invstd=None,
@@ -484,6 +553,7 @@ def instrument(monkeypatch, chk):
         def wrap(*a, _f=fn, _n=name, **k):
             chk.called.add(_n)
             chk.flush()
+            chk.note(_n, a, k)
             handler = getattr(chk, _n, None)
             if handler is None:
                 return _f(*a, **k)
@@ -505,6 +575,28 @@ def instrument(monkeypatch, chk):
         monkeypatch.setattr(ops, name, wrap)
 
 
+def run_checked_step(name, model, step, dtype, vol, lab, monkeypatch):
+    """One warm-up step, then one instrumented step; every recorded signature was checked and nothing called is unrestated.  Returns the Checker."""
+    step.step(vol, lab)                                    # warm-up: packs the weights, picks every launch once
+    torch.cuda.synchronize()
+    ex = model._exec
+    sd = ex._sd()
+    weights = {buf.data_ptr(): (sd[name_], kind) for (name_, kind), buf in ex._packed[dtype]["bufs"].items()}
+    chk = Checker(weights, dtype)
+    instrument(monkeypatch, chk)
+    step.step(vol, lab)
+    torch.cuda.synchronize()
+    chk.flush()
+    monkeypatch.undo()
+    print("\n%s: %d signatures checked" % (name, len(chk.checked)))
+    for line in chk.lines:
+        print("  " + line)
+    assert chk.checked == chk.recorded and chk.checked
+    unrestated = {n for n in chk.called if not hasattr(Checker, n)}
+    assert unrestated <= set(EXCLUDED), sorted(unrestated - set(EXCLUDED))
+    return chk
+
+
 @pytest.mark.parametrize("dtype_name", ["bf16", "fp32"])
 @pytest.mark.parametrize("cfg", ["2d", "3d"])
 def test_every_launch_of_one_step(cfg, dtype_name, monkeypatch):
@@ -516,20 +608,62 @@ def test_every_launch_of_one_step(cfg, dtype_name, monkeypatch):
     random.seed(1337)
     model, step, dtype = bench.build_step(cfg, dtype_name, B, sp, 1, {"concurrent": False}, 1, DEV)
     vol, lab = bench.synthetic(cfg, 1337, B, sp, DEV)
-    step.step(vol, lab)                                    # warm-up: packs the weights, picks every launch once
-    torch.cuda.synchronize()
-    ex = model._exec
-    sd = ex._sd()
-    weights = {buf.data_ptr(): (sd[name], kind) for (name, kind), buf in ex._packed[dtype]["bufs"].items()}
-    chk = Checker(weights, dtype)
-    instrument(monkeypatch, chk)
-    step.step(vol, lab)
-    torch.cuda.synchronize()
-    chk.flush()
-    monkeypatch.undo()
-    print("\n%s %s: %d signatures checked" % (cfg, dtype_name, len(chk.checked)))
-    for line in chk.lines:
-        print("  " + line)
-    assert chk.checked == chk.recorded and chk.checked
-    unrestated = {n for n in chk.called if not hasattr(Checker, n)}
-    assert unrestated <= set(EXCLUDED), sorted(unrestated - set(EXCLUDED))
+    run_checked_step("%s %s" % (cfg, dtype_name), model, step, dtype, vol, lab, monkeypatch)
+
+
+RESIDUAL_SP = (16, 16, 48)
+
+
+@pytest.mark.parametrize("dtype_name", ["bf16", "fp32"])
+def test_every_launch_of_one_residual_step(dtype_name, monkeypatch):
+    """Every launch of one training iteration of the RESIDUAL 3D net (DualDecoder3d(has_residual=True, has_dropout=True), VAT on), as above: the step is
+    built with bench.build_step's lines for the 3D configuration (which builds the plain nets only), run eagerly, ungrouped, on one stream.  Beyond the
+    plain step's launches it checks residual_fwd (image / one source / up + skip), residual_bwd (with chan_mul on a dropped block output, with dxin in
+    block_one), grad_sum (the program-order fold of a skip feature's five contributions, from the very tensors the executor passed), perturb as
+    dx += dxin, and bn_finalize / conv_fwd / wgrad / act_bwd on Lazies with act=False (a BatchNorm with no activation behind it) and on residual
+    outputs (no affine, with and without Dropout3d multipliers, alone or as the second operand of the skip add).
+
+    Shape: B = 4 (2 labelled + 2 unlabelled; the executor passes N = 2 per pass) at 16 x 16 x 48, the smallest multiple of 16 per axis (five levels)
+    at which the bf16 step still takes conv bricks (level 0: 2 * 4 * 4 * 3 = 96 bricks >= 64), the K-parallel route, the 1x1x1 head, weight-gradient
+    bricks with 16-wide (level 0) and 32-wide B tiles (level 1: 2 * 2 * 2 * 2 = 16 bricks >= CHAP_WGRAD_BRICK's 16; 16 x 16 x 32 gives 8) and
+    weight-gradient slabs.  Routes of the 3x3x3 layers per level from the host-only planner (conv_plan.h / wgrad_plan.h through the probe of
+    tests/test_launch_plan_cpu.py, N = 2), conv = forward and input-gradient conv of one source / add-combined forward conv:
+
+      bf16   level  channels   112 x 112 x 80                                      16 x 16 x 48
+             0      16         conv bricks NT1 MR4          wgrad brick bn16       conv bricks NT1 MR4          wgrad brick bn16
+             1      32         conv bricks NT2 MR4          wgrad brick bn32       conv slabs NT2 MR1           wgrad brick bn32
+             2      64         conv bricks NT2 MR4          wgrad brick bn32       kpar cpar4 / slabs NT4 MR1   wgrad slab KC32
+             3      128        kpar cpar4 / slabs NT4 MR1   wgrad brick bn32       kpar cpar4 / slabs NT4 MR1   wgrad slab KC32
+             4      256        kpar cpar4 / slabs NT4 MR1   wgrad slab KC32        kpar cpar4 / slabs NT4 MR1   wgrad slab KC32
+             head   16 -> 2    conv_head1x1                                        conv_head1x1
+      fp32   0 .. 4            slabs NT1 / NT2 / NT4 / NT4 / NT4, MR1; wgrad slab KC16 / KC32 / KC32 / KC32 / KC32: the same at both shapes
+
+    What the full-size step takes and this one cannot reach (a brick conv needs >= 64 bricks, and from 128 up it takes NT2): the bf16 brick conv with
+    32 K-channels and NT2 and the one with 64 K-channels (four chunks), both also add-combined -- covered with residual-style sources by
+    tests/test_kernels_gpu.py::test_conv3d_residual_sources[brick32 / brick64]; the weight-gradient bricks with 64 and 128 A channels are the
+    bn32 instance of level 1 with more chunks -- tests/test_kernels_bwd_gpu.py::test_wgrad_conv3d_residual_sources forces the bricks onto 32 -> 32
+    and 64 -> 128."""
+    from chap_amd.networks import DualDecoder3d
+    from chap_amd.train import ChapStep
+    monkeypatch.setenv("CHAP_GROUP", "0")
+    B, sp = 4, RESIDUAL_SP
+    np.random.seed(1337)
+    random.seed(1337)
+    dtype = torch.bfloat16 if dtype_name == "bf16" else torch.float32
+    torch.manual_seed(1337)                                 # bench.build_step's lines for the 3D configuration, with has_residual=True
+    model = DualDecoder3d(n_channels=1, n_classes=2, normalization="batchnorm", has_dropout=True, has_residual=True).to(DEV).train().set_compute_dtype(dtype)
+    step = ChapStep(model, dict(batch_size=B, labeled_bs=B // 2, vat_iters=1, num_classes=2, concurrent=False), world_size=1)
+    vol, lab = bench.synthetic("3d", 1337, B, sp, DEV)
+    chk = run_checked_step("3d residual %s" % dtype_name, model, step, dtype, vol, lab, monkeypatch)
+    # the residual path's own launches were among the checked signatures (key = (op, sig(args), sig(kwargs)); a Lazy's sig: ..., has scale, act, ...)
+    ops_seen = {k[0] for k in chk.checked}
+    assert {"residual_fwd", "residual_bwd", "grad_sum", "perturb", "act_bwd", "conv_fwd", "wgrad", "bn_finalize"} <= ops_seen
+    kw = lambda k: dict(k[2])
+    assert any(k[0] == "residual_fwd" and kw(k).get("xin") is not None for k in chk.checked)                   # block_one: the image as the block's input
+    assert any(k[0] == "residual_fwd" and len(k[1][1]) == 2 for k in chk.checked)                               # a decoder block: up + skip
+    assert any(k[0] == "residual_bwd" and kw(k).get("dxin") is not None for k in chk.checked)
+    assert any(k[0] == "residual_bwd" and kw(k).get("dxin") is None and kw(k).get("chan_mul") is not None for k in chk.checked)
+    assert chk.cm_matched > 0                                                                                   # ... and it was the consumers' multiplier (Checker.note)
+    assert any(k[0] == "grad_sum" for k in chk.checked)
+    assert any(k[0] == "perturb" and k[1][0][1] != k[1][1][1] for k in chk.checked)                             # dx [N, 1, D, H, W] += dxin [N, D*H*W]
+    assert any(k[0] == "act_bwd" and k[1][0][5] and not k[1][0][6] for k in chk.checked)                        # a BatchNorm with no activation behind it

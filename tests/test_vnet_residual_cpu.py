@@ -206,3 +206,31 @@ def test_new_structs_match_the_header(tmp_path):
         st, f = pairs[name]
         assert int(size) == ctypes.sizeof(st), (name, size, ctypes.sizeof(st))
         assert int(off) == getattr(st, f).offset, (name, off)
+
+
+def test_more_than_three_contributions_fold_the_oldest_first():
+    """The executor's fold of a value's gradient contributions (engine.fold_oldest_first, used by backward's incoming3): chap_act_bwd_* and
+    chap_residual_bwd take three, chap_grad_sum up to four.  A skip feature of a residual DualDecoder3d has five -- the down conv and, per decoder,
+    the block's first conv and its residual add, in program order: ((c0 + c1) + c2) by chap_grad_sum, then ((t + c3) + c4) in the consumer.
+    Symbolic summands here; the per-launch values are checked in tests/test_step_launches_gpu.py."""
+    from chap_amd.engine import fold_oldest_first
+    calls = []
+
+    def fold(group):
+        calls.append(list(group))
+        return tuple(group)
+
+    assert fold_oldest_first(None, fold) is None and fold_oldest_first([], fold) == [] and fold_oldest_first([0, 1, 2], fold) == [0, 1, 2] and not calls
+    assert fold_oldest_first([0, 1, 2, 3], fold) == [(0, 1), 2, 3]
+    assert fold_oldest_first([0, 1, 2, 3, 4], fold) == [(0, 1, 2), 3, 4]
+    assert fold_oldest_first([0, 1, 2, 3, 4, 5], fold) == [(0, 1, 2, 3), 4, 5]
+    assert fold_oldest_first(list(range(8)), fold) == [((0, 1, 2, 3), 4, 5), 6, 7]              # two launches: four, then the sum and two more
+    assert all(2 <= len(g) <= 4 for g in calls)                                                  # what chap_grad_sum accepts
+    # the net that needs it: every skip feature of the residual DualDecoder3d is read by five ops, block outputs elsewhere by fewer
+    from chap_amd.networks.vnet import build_program
+    prog = build_program(2, 16, [("decoder1", 0), ("decoder2", 0)], True, has_residual=True)
+    readers = {}
+    for op in prog.ops:
+        for sname in op.srcs:
+            readers[sname] = readers.get(sname, 0) + 1
+    assert sorted(readers.values())[-4:] == [5, 5, 5, 5] and max(readers.values()) == 5

@@ -170,15 +170,18 @@ def test_training_iteration_eager_equals_captured():
     """ChapStep on DualDecoder3d(has_residual=True, has_dropout=True), 2 labelled + 2 unlabelled samples at 32 x 32 x 16, VAT on: three eager steps
     (decoders on two streams, deferred decoder weight gradients) against capture + three replays (pass B and the early VAT pass run the
     decoders in lockstep: the residual adds of the two decoders are the lanes of grouped launches) -- losses and the flat parameter buffer bit
-    for bit, losses finite.  The loss VALUES are not compared with a restatement: no oracle restates the residual iteration
-    (oracle.train_step drives the plain nets)."""
+    for bit, losses finite.  The loss VALUES are tied to the oracle: the eager run's mix_losses of the first step against
+    oracle.train_step.iteration driving the residual restatement (net=tests.vnet_residual_ref.dual_decoder_3d) in fp32 with the same injected
+    randomness, within the 5e-4 (max norm, relative) of tests/test_iteration_conditioning_gpu.py's small 3D cases; the whole iteration is judged there
+    (test_small_3d_residual_iteration_is_as_close_to_fp64_as_the_fp32_oracle)."""
     from chap_amd.train import ChapStep
     from oracle import train_step as ots
-    from tests.iteration_parity import inject_3d, to_dev
+    from tests.iteration_parity import _rel, inject_3d, run_oracle, to_dev
     B, lbs, sp = 4, 2, (32, 32, 16)
     state = oinit.dual_decoder_3d_state(401)
     vol, lab = ots.synthetic_batch_3d(1337, lbs, B - lbs, *sp)
-    inj = to_dev(inject_3d(B - lbs, lbs // 2 + (B - lbs) // 2, sp, 1), 3)
+    inj_cpu = inject_3d(B - lbs, lbs // 2 + (B - lbs) // 2, sp, 1)
+    inj = to_dev(inj_cpu, 3)
     box = (4, 5, 3)
     res = {}
     for mode in ("eager", "graph"):
@@ -200,3 +203,10 @@ def test_training_iteration_eager_equals_captured():
         for s, t in zip(a, b):
             assert torch.isfinite(s).all() and torch.equal(s, t), (s, t)
     assert torch.equal(res["eager"][1], res["graph"][1])
+    # ... and the bit-for-bit pair has the oracle's values: the first step's mix losses against the fp32 oracle of the residual iteration
+    args = dict(labeled_bs=lbs, batch_size=B, vat_iters=1, num_classes=2, adv_noise=True)
+    o32 = run_oracle(state, vol, lab, box, 4500, args, inj_cpu, 3, torch.float32, residual=True)
+    got = torch.stack([t.double().cpu() for t in res["eager"][0][0][:-1]])
+    e = _rel(got, o32["losses"])
+    print("first step's mix losses against the fp32 oracle: %.3g" % e)
+    assert got.shape == o32["losses"].shape and e < 5e-4
