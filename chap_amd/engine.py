@@ -11,6 +11,9 @@ into the model's flat gradient buffer.
 
 Reference semantics followed: code/networks/unet.py:44-292, code/networks/vnet.py:8-238.
 """
+import itertools
+import os
+
 import torch
 
 from . import _lib as L
@@ -98,65 +101,92 @@ def fold_oldest_first(c, fold, limit=3, width=4):
     return c
 
 
-def drive(gen, stream):
-    """Run a step generator (Executor.forward_steps / backward_steps): the lanes of a step -- the same-shaped ops of the two decoders --
-    are enqueued inside ONE grouped launch region (their kernels become one grid), a single lane directly.  Returns the generator's
-    return value."""
-    while True:
-        try:
-            lanes = next(gen)
-        except StopIteration as e:
-            return e.value
-        if not lanes:
-            continue
-        if len(lanes) == 1:
-            lanes[0]()
-        else:
-            with L.group(stream) as region:
-                for k, f in enumerate(lanes):
-                    if k:
-                        region.next_lane()
-                    f()
+# ---------------------------------------------------------------------------------------------------------------- lab switches
+# The Python side's lab / A-B switches, one row each: name -> (default, parse(value string), meaning).  They are LIVE: switch() reads the
+# environment every time it is asked (tests flip CHAP_GROUP inside one process), except CHAP_FORK_MASK, which ChapStep reads once per captured
+# iteration.  (The C side's table is csrc/knobs.h; CHAP_LIBPATH belongs to _lib.py.)
+_on_unless_0 = lambda v: v != "0"       # noqa: E731
+SWITCHES = {
+    "CHAP_GROUP": ("1", int,
+                   "0 = never group (round 2: decoders back to back where a pass cannot fork a second stream), 1 = group the two decoders' same-shaped "
+                   "layers in the passes that cannot fork one.  (Round 3 also measured grouping in EVERY pass, the decoders as parallel graph branches on "
+                   "one stream and the weight gradients as graph leaves: all slower, removed -- DESIGN.md section 5.)"),
+    "CHAP_SIDE_DECODER": ("1", lambda v: 2 if v == "2" else 1,
+                          "which decoder of a forking pass runs on the forked stream (the other stays on the pass's own).  Round 4, two runs each: 2D "
+                          "6.413 / 6.421 ms with decoder 2 on the fork, 6.385 / 6.407 with decoder 1; 3D 14.82 / 14.70 vs 14.66 / 14.62 "
+                          "(profiles/r04_side_decoder_ab.log)."),
+    "CHAP_C1_DIRECT": ("1", _on_unless_0,
+                       "the first conv (one input channel) of a bf16 pass on its own kernel (csrc/conv_c1_mfma.h) instead of the generic conv over the image "
+                       "zero-padded to 16 channels."),
+    "CHAP_DEFER_WGRAD": ("1", _on_unless_0,
+                         "in a backward pass that forks its second decoder, the decoders' weight gradients are issued on the forked stream BEHIND both "
+                         "decoders' chains -- they are not on the path to the join with the trunk, and the forked stream used to idle during the trunk's "
+                         "backward.  Round 4, three pairs: 2D 6.24 / 6.22 / 6.26 -> 6.09 / 6.09 / 6.11 ms, 3D 14.68 / 14.61 / 14.69 -> 14.64 / 14.60 / 14.51 ms.  "
+                         "Tried on top and removed: the trunk's weight gradients on that stream too, one event per layer (6.6 / 15.3 ms); pass B (grouped "
+                         "decoders on one stream) borrowing the early VAT pass's idle stream for its decoders' weight gradients (7.65 / 17.3 ms: one more "
+                         "chain for the graph executor's queues); the forked decoder's own weight gradients right behind its chain instead of behind both "
+                         "(no difference) -- profiles/r04_defer_wgrad_ab.log."),
+    "CHAP_SPLIT_CONCAT": ("1", _on_unless_0, "the input gradient of a concat layer as two dense tensors (chap_conv_params.out2)."),
+    "CHAP_FORK_MASK": ("14", int,
+                       "which passes on the capture's origin stream fork their second decoder onto a stream of its own (train.FORK_PASS_A = 1, "
+                       "FORK_POWER_BACKWARD = 2, FORK_VAT_FORWARD = 4, FORK_FINAL_BACKWARD = 8); the others run their decoders with grouped launches.  Every "
+                       "fork is one more chain for the graph executor to place on its few hardware queues (DESIGN.md section 5, \"Issue order\").  Round 4, "
+                       "12 masks on the whole iteration (profiles/r04_issue_order_ab.log): 14 -- pass A, which already shares the GPU with the early VAT "
+                       "pass, keeps its decoders on one stream -- 6.469 ms against 6.513 for 15 (three pairs; 3D 14.79 vs 14.81), every other mask slower "
+                       "(0: 6.83 / 15.8)."),
+}
 
 
-def side_branch():
-    """CHAP_SIDE_DECODER (lab / A-B switch, default 1): which decoder of a forking pass runs on the forked stream (the other stays on the pass's
-    own).  Round 4, two runs each: 2D 6.413 / 6.421 ms with decoder 2 on the fork, 6.385 / 6.407 with decoder 1; 3D 14.82 / 14.70 vs 14.66 / 14.62
-    (profiles/r04_side_decoder_ab.log)."""
-    import os
-    return 2 if os.environ.get("CHAP_SIDE_DECODER", "1") == "2" else 1
+def switch(name):
+    """The current value of a lab switch of SWITCHES (the one place of engine.py / train.py that reads the environment for them)."""
+    default, parse, _ = SWITCHES[name]
+    return parse(os.environ.get(name, default))
 
 
-def first_conv_direct():
-    """CHAP_C1_DIRECT (lab / A-B switch, default 1): the first conv (one input channel) of a bf16 pass on its own kernel (csrc/conv_c1_mfma.h) instead
-    of the generic conv over the image zero-padded to 16 channels."""
-    import os
-    return os.environ.get("CHAP_C1_DIRECT", "1") != "0"
+# ---------------------------------------------------------------------------------------------------------------- the order of a pass
+GROUPED, FORKED, SERIAL = "grouped", "forked", "serial"     # how a pass runs its two decoders (Executor._decoder_mode)
+OWN, FORK, JOIN = "own", "fork", "join"                     # where a step of the schedule is issued
 
 
-def defer_decoder_wgrad():
-    """CHAP_DEFER_WGRAD (lab / A-B switch, default 1): in a backward pass that forks its second decoder, the decoders' weight gradients are issued on the
-    forked stream BEHIND both decoders' chains -- they are not on the path to the join with the trunk, and the forked stream used to idle during the trunk's
-    backward.  Round 4, three pairs: 2D 6.24 / 6.22 / 6.26 -> 6.09 / 6.09 / 6.11 ms, 3D 14.68 / 14.61 / 14.69 -> 14.64 / 14.60 / 14.51 ms.  Tried on top and
-    removed: the trunk's weight gradients on that stream too, one event per layer (6.6 / 15.3 ms); pass B (grouped decoders on one stream) borrowing the early
-    VAT pass's idle stream for its decoders' weight gradients (7.65 / 17.3 ms: one more chain for the graph executor's queues); the forked decoder's own
-    weight gradients right behind its chain instead of behind both (no difference) -- profiles/r04_defer_wgrad_ab.log."""
-    import os
-    return os.environ.get("CHAP_DEFER_WGRAD", "1") != "0"
+def pass_schedule(prog, mode, side_decoder=1, backward=False):
+    """The ISSUE order of one pass over `prog`, as data: a list of steps (where, ops).  where = OWN: on the pass's own stream, `ops` is one op or
+    the same-shaped ops of the two decoders, which become the lanes of ONE grouped launch region; FORK: one op on the forked stream; JOIN (no ops):
+    the point behind the decoders where the forked stream's chain meets the pass's own stream again.  Pure: no device, no environment.
+
+    Forward: the trunk, then the decoders.  Backward: the decoders, each in reverse, then the trunk in reverse.  The decoders, by `mode`:
+      GROUPED  in lockstep, the pairs of zip_branches: same-shaped layers (ConvBlock convs, their BatchNorm finalizes, the heads) are the two lanes of
+               ONE grouped launch (chap_hip.h, chap_group_*): half the launches of the decoder part, twice the tiles per launch, and no second stream
+               (which a captured pass on a forked stream could not have, see Executor._side_stream);
+      FORKED   on two streams: the ops of decoder `side_decoder` on the forked stream are issued first, then the other one's, then the join -- in
+               both directions.  (Round 4 tried them alternately, op by op: neutral, 6.55 vs 6.5 ms; the ISSUE order is the creation order of a
+               captured graph's nodes, by which the ROCm 7.2 graph executor places the chains on its hardware queues: DESIGN.md section 5, "Issue
+               order" -- any change here has to be measured on the whole iteration.);
+      SERIAL   back to back in program order."""
+    trunk = [(OWN, (op,)) for op in prog.ops if op.branch == 0]
+    dec = [op for op in prog.ops if op.branch != 0]
+    if mode == GROUPED:
+        blocks = [[(OWN, lanes) for lanes in zip_branches([op for op in dec if op.branch == 1], [op for op in dec if op.branch == 2])]]
+    elif mode == FORKED:
+        forked = [(op.branch >= 2) == (side_decoder == 2) for op in dec]
+        blocks = [[(FORK, (op,)) for op, f in zip(dec, forked) if f], [(OWN, (op,)) for op, f in zip(dec, forked) if not f], [(JOIN, ())]]
+    else:
+        blocks = [[(OWN, (op,)) for op in dec]]
+    if backward:
+        return [step for b in blocks for step in reversed(b)] + trunk[::-1]
+    return trunk + [step for b in blocks for step in b]
 
 
-def split_concat_gradient():
-    """CHAP_SPLIT_CONCAT (lab / A-B switch, default 1): the input gradient of a concat layer as two dense tensors (chap_conv_params.out2)."""
-    import os
-    return os.environ.get("CHAP_SPLIT_CONCAT", "1") != "0"
-
-
-def grouping_mode():
-    """CHAP_GROUP (lab / A-B switch): 0 = never group (round 2: decoders back to back where a pass cannot fork a second stream), 1 (default) =
-    group the two decoders' same-shaped layers in the passes that cannot fork one.  (Round 3 also measured grouping in EVERY pass, the
-    decoders as parallel graph branches on one stream and the weight gradients as graph leaves: all slower, removed -- DESIGN.md section 5.)"""
-    import os
-    return int(os.environ.get("CHAP_GROUP", "1"))
+def issue_lanes(fn, items, stream):
+    """fn(item) for every item of one step: a single one directly; several as the lanes of ONE grouped launch region (their kernels become one
+    grid) on `stream`; none: nothing."""
+    if len(items) == 1:
+        fn(items[0])
+    elif items:
+        with L.group(stream) as region:
+            for k, item in enumerate(items):
+                if k:
+                    region.next_lane()
+                fn(item)
 
 
 class Saved:
@@ -185,6 +215,9 @@ class Executor:
         self._ident = {}           # C -> (ones, zeros) for InstanceNorm (no affine)
         self._sides = {}           # parent stream -> forked stream for the second decoder
         self._capture_sides = {}   # same, for use inside a graph capture (registered by the owner of the capture)
+        self._schedules = {}       # (mode, side decoder, backward) -> pass_schedule(...)
+        self.nbranch = len({op.branch for op in program.ops})      # trunk + decoders
+        self.ntrunk = sum(op.branch == 0 for op in program.ops)    # the trunk's steps: the head of a forward schedule, the tail of a backward one
         self.has_inorm = any(op.inorm for op in program.ops)
 
     # ---------------------------------------------------------------- parameters
@@ -222,13 +255,43 @@ class Executor:
         return dims
 
     def _zipped(self):
-        """The aligned schedule of the two decoder branches (zip_branches), built once per program."""
-        z = getattr(self, "_zip", None)
-        if z is None:
-            b1 = [op for op in self.prog.ops if op.branch == 1]
-            b2 = [op for op in self.prog.ops if op.branch == 2]
-            z = self._zip = zip_branches(b1, b2)
-        return z
+        """The lockstep pairs of the two decoder branches (zip_branches), as the grouped schedule holds them."""
+        return [lanes for _, lanes in self._schedule(GROUPED, False) if lanes[0].branch != 0]
+
+    def _decoder_mode(self, cur_stream):
+        """How a pass on `cur_stream` runs its two decoders -> (mode, forked stream or None): FORKED where this pass may fork a second stream (eager;
+        under capture only from the capture's origin stream, see _side_stream), otherwise GROUPED (trunk + two decoders, CHAP_GROUP != 0), else SERIAL."""
+        side = self._side_stream(cur_stream) if self.nbranch > 2 else None
+        if side is not None:
+            return FORKED, side
+        return (GROUPED if self.nbranch == 3 and switch("CHAP_GROUP") != 0 else SERIAL), None
+
+    def _schedule(self, mode, backward):
+        """pass_schedule of this program, built once per (mode, decoder on the fork, direction)."""
+        key = (mode, switch("CHAP_SIDE_DECODER") if mode == FORKED else 1, backward)
+        sched = self._schedules.get(key)
+        if sched is None:
+            sched = self._schedules[key] = pass_schedule(self.prog, *key)
+        return sched
+
+    @staticmethod
+    def _issue(steps, fn, cur_stream, side, join=None):
+        """The one interpreter of a schedule, for both directions: fn(op) for every op in the order of `steps` -- a single op directly, several lanes
+        inside one grouped launch region, the forked block on `side` between side.wait_stream(cur_stream) and the JOIN step (`join()`; default: the
+        pass's own stream waits for the forked one)."""
+        for where, block in itertools.groupby(steps, key=lambda step: step[0]):
+            if where == FORK:
+                side.wait_stream(cur_stream)
+                with torch.cuda.stream(side):
+                    for _, (op,) in block:
+                        fn(op)
+            elif where == JOIN and join is not None:
+                join()
+            elif where == JOIN:
+                cur_stream.wait_stream(side)
+            else:
+                for _, lanes in block:
+                    issue_lanes(fn, lanes, cur_stream.cuda_stream)
 
     def _pack_kinds(self, op):
         if op.kind == "conv":
@@ -281,15 +344,9 @@ class Executor:
         return self._ensure_packed(dtype, sd)["bufs"][(op.w, kind)]
 
     # ---------------------------------------------------------------- forward
-    def forward(self, x, **kw):
+    def forward(self, x, *, train, dtype, save, update_stats=True, drop_masks=None, rng=None, want=(), perturb=None):
         """x: fp32 [N, in_chns, *spatial] contiguous. Returns (list of planar fp32 logits, Saved|None, extras):
         extras = the activated values named in `want`, materialised as planar fp32 [N, C, *spatial]."""
-        return drive(self.forward_steps(x, **kw), torch.cuda.current_stream().cuda_stream)
-
-    def forward_steps(self, x, *, train, dtype, save, update_stats=True, drop_masks=None, rng=None, want=(), perturb=None):
-        """The forward pass as a generator of STEPS: each `yield` hands the driver (engine.drive) the lanes of one step -- a list
-        of callables that enqueue the step's kernels, one per lane (one op; or the same-shaped ops of the two decoders, which the
-        driver issues as ONE grouped launch region: chap_hip.h, chap_group_*) -- and the generator's return value is forward()'s."""
         prog, sd, dims = self.prog, self._sd(), self.prog.dims
         dev = x.device
         N = x.shape[0]
@@ -328,11 +385,7 @@ class Executor:
 
         outs = {}
         cur_stream = torch.cuda.current_stream()
-        branches = sorted({op.branch for op in prog.ops})
-        # two decoders: on a second stream where this pass may fork one (eager; under capture only from the capture's origin
-        # stream), otherwise in lockstep with grouped launches
-        side = self._side_stream(cur_stream) if len(branches) > 2 else None
-        zipped = self._zipped() if (side is None and len(branches) == 3 and grouping_mode() != 0) else None
+        mode, side = self._decoder_mode(cur_stream)
 
         # Dropout seeds are drawn HERE, in program order: the order in which the ops are ISSUED depends on whether this pass
         # may fork its second decoder (eager / captured, which stream), and a seed must not (round 2: the early VAT pass drew
@@ -343,7 +396,7 @@ class Executor:
                 if op_.drop:
                     drop_seed[id(op_)] = rng.next_seed()
         # The element keep masks of the trunk (nn.Dropout of the five encoder ConvBlocks) depend on nothing but their seeds: they are
-        # generated up front, as the lanes of one step (same-sized ones share a grid), instead of one launch on the chain behind each conv
+        # generated up front, as the lanes of ONE step (same-sized ones share a grid), instead of one launch on the chain behind each conv
         pre_keep = {}
         if train:
             elem = [op_ for op_ in prog.ops if op_.drop and op_.drop[2] == "elem" and op_.branch == 0 and op_.kind in ("c1", "conv")] if drop_masks is None else []
@@ -353,7 +406,7 @@ class Executor:
                 keep = L.hold_empty((N,) + sdims[op_.out] + (op_.cout,), dtype=torch.uint8, device=dev)
                 ops.keep_mask(keep, drop_seed[id(op_)], op_.drop[1], seed_dev=rng.seed_dev)
                 pre_keep[id(op_)] = keep
-            yield [lambda op_=op_: make_keep(op_) for op_ in elem]        # (a step of every training-mode pass, possibly without lanes: passes driven together stay aligned)
+            issue_lanes(make_keep, elem, cur_stream.cuda_stream)
 
         def apply_drop(op, lz, out, n):
             """Dropout on the OUTPUT value of `op` (training mode): the keep mask / channel multiplier its consumers apply while loading."""
@@ -424,7 +477,7 @@ class Executor:
             if k == "c1":
                 gd = (D, H, W)
                 out = L.hold_empty(n, D, H, W, op.cout, dtype=dtype, device=dev)
-                if dtype == torch.bfloat16 and x.shape[1] == 1 and op.cout == 16 and first_conv_direct():
+                if dtype == torch.bfloat16 and x.shape[1] == 1 and op.cout == 16 and switch("CHAP_C1_DIRECT"):
                     # bf16, one input channel: the taps as the K dimension of one MFMA per 16 pixels (csrc/conv_c1_mfma.h) -- no zero-padded copy of the
                     # image; the backward pass builds it when (and only when) it needs the weight gradient
                     ops.conv_c1_fwd(x.view(n, D, H, W), sd[op.w], bias, out, dims=dims, stats=stats, stats_shift=sshift)
@@ -494,45 +547,21 @@ class Executor:
             if op.drop and train:
                 apply_drop(op, lz, out, n)
             V[op.out] = lz
-        # ---- schedule: trunk, then the decoders side by side (second decoder on a forked stream)
-        for op in prog.ops:
-            if op.branch == 0:
-                yield [lambda op=op: run_op(op)]
+        # ---- schedule (pass_schedule): the trunk, then the decoders in lockstep, on two streams or back to back
+        steps = self._schedule(mode, False)
+        self._issue(steps[:self.ntrunk], run_op, cur_stream, side)
         if perturb is not None:
             # channel-level perturbation (FilterDropout.perform_dropout): every decoder gets its own version of the
             # trunk's values -- a larger batch with per-(sample, channel) multipliers -- and runs on that batch
             overlays, n_dec = perturb(vals, vdims)
-            tables = {b: dict(vals, **overlays[b]) for b in branches if b != 0}
+            tables = {b: dict(vals, **overlays[b]) for b in overlays}
             if save:
                 S.tables, S.n_dec = tables, n_dec
                 S.fold = {b: {name: lz.chan_mul for name, lz in overlays[b].items()} for b in tables}
             run_dec = lambda op: run_op(op, tables[op.branch], n_dec)      # noqa: E731
         else:
             run_dec = run_op
-        if zipped is not None:
-            # the two decoders in lockstep: same-shaped layers (ConvBlock convs, their BatchNorm finalizes, the heads) are the two lanes
-            # of ONE grouped launch (chap_hip.h, chap_group_*): half the launches of the decoder part, twice the tiles per launch,
-            # and no second stream (which a captured pass on a forked stream could not have, see _side_stream)
-            for pair in zipped:
-                yield [lambda op=op: run_dec(op) for op in pair]
-        elif side is not None:
-            # two streams: the forked decoder's ops are issued first, then the other one's.  (Round 4 tried them alternately, op by op: neutral, 6.55 vs 6.5 ms;
-            # the ISSUE order is the creation order of a captured graph's nodes, by which the ROCm 7.2 graph executor places the chains on its hardware
-            # queues: DESIGN.md section 5, "Issue order" -- any change here has to be measured on the whole iteration.)
-            side.wait_stream(cur_stream)
-            sb = side_branch()                  # which decoder goes to the forked stream
-            with torch.cuda.stream(side):
-                for op in prog.ops:
-                    if op.branch != 0 and (op.branch >= 2) == (sb == 2):
-                        run_dec(op)
-            for op in prog.ops:
-                if op.branch != 0 and (op.branch >= 2) != (sb == 2):
-                    run_dec(op)
-            cur_stream.wait_stream(side)
-        else:
-            for op in prog.ops:
-                if op.branch != 0:
-                    yield [lambda op=op: run_dec(op)]
+        self._issue(steps[self.ntrunk:], run_dec, cur_stream, side)
         logits = [outs[h] for h in prog.heads]
         extras = []
         for name in want:
@@ -543,13 +572,9 @@ class Executor:
         return logits, (S if save else None), extras
 
     # ---------------------------------------------------------------- backward
-    def backward(self, S, dlogits, **kw):
+    def backward(self, S, dlogits, *, dtype, need_wgrad, need_dx, grad_buffer=None):
         """dlogits: list (per head) of planar fp32 gradients or None. Accumulates parameter gradients
         into the module's flat grad views; returns dx (fp32, shape of x) or None."""
-        return drive(self.backward_steps(S, dlogits, **kw), torch.cuda.current_stream().cuda_stream)
-
-    def backward_steps(self, S, dlogits, *, dtype, need_wgrad, need_dx, grad_buffer=None):
-        """The backward pass as a generator of steps (see forward_steps); returns dx."""
         prog, sd, dims = self.prog, self._sd(), self.prog.dims
         gr = None
         if need_wgrad:
@@ -591,23 +616,24 @@ class Executor:
             spos[0] += n
             return t
 
-        # the weight gradients of the two decoders are not on the path to the join with the trunk: deferred (defer_decoder_wgrad), they are issued on the
+        cur_stream = torch.cuda.current_stream()
+        mode, side = self._decoder_mode(cur_stream)
+        # the weight gradients of the two decoders are not on the path to the join with the trunk: deferred (CHAP_DEFER_WGRAD), they are issued on the
         # forked stream BEHIND both decoders' chains and run beside the trunk's backward, where that stream used to idle.  The closures stay in `deferred`
-        # until this generator ends, i.e. until the streams have joined: they keep the gradient tensors alive (freed earlier, a tensor goes back to the
+        # until this function returns, i.e. until the streams have joined: they keep the gradient tensors alive (freed earlier, a tensor goes back to the
         # allocator of ITS stream and is handed out again while the forked stream still reads it)
         deferred = []
-        defer_on = [False]
+        defer = side is not None and need_wgrad and switch("CHAP_DEFER_WGRAD")
 
         def later(op, fn):
-            if defer_on[0] and op.branch != 0:
+            if defer and op.branch != 0:
                 deferred.append(fn)
             else:
                 fn()
 
         def scatter(op, srcs, dsrc):
-            muls = S.fold.get(op.branch) if S.tables is not None else None
-            if not muls:
-                return self._scatter(contrib, op, srcs, dsrc, okey[id(op)])
+            """dsrc = the gradient w.r.t. the op's input -> one contribution per source: its channel slice of a concatenation (combine == 0), all of a sum."""
+            muls = (S.fold.get(op.branch) if S.tables is not None else None) or ()
             off = 0
             for name, s in zip(op.srcs, srcs):
                 o = off if op.combine == 0 else 0
@@ -732,7 +758,7 @@ class Executor:
                                                 ksize=op.ksize, stride=1, dims=dims, combine=op.combine, db=gr[op.b] if op.b else None, kn_valid=kn_valid))
                 wp = self._pack(op, L.PACK_CONV_DGRAD, dtype, sd)
                 if (len(srcs) == 2 and op.combine == 0 and op.ksize == 3 and srcs[0].C == srcs[1].C and srcs[0].C % 16 == 0 and S.tables is None
-                        and split_concat_gradient()):
+                        and switch("CHAP_SPLIT_CONCAT")):
                     # the input was torch.cat((skip, up), 1) (unet.py:98): its gradient as two DENSE tensors, one per source (chap_conv_params.out2) -- the
                     # BatchNorm backward of either source then reads whole 32-byte sectors instead of a 16-channel slice of a 32-channel row (round 3:
                     # FETCH_SIZE 1.25 x the algorithmic bytes of act_bwd at C = 16, 256 x 256)
@@ -769,64 +795,27 @@ class Executor:
                 dsrc = L.hold_empty(n, sd_, sh_, sw_, ctot, dtype=dtype, device=dev)
                 ops.conv_fwd([g], wp, None, ctot, dsrc, grid=(n, sd_, sh_, sw_), in_dims=fine, ksize=2, stride=2, dims=dims)
                 scatter(op, srcs, dsrc)
-        # ---- schedule: the decoders' backward passes side by side, then the shared trunk
-        cur_stream = torch.cuda.current_stream()
-        rev = list(reversed(prog.ops))
-        nbr = len({op.branch for op in prog.ops})
-        side = self._side_stream(cur_stream) if nbr > 2 else None
-        zipped = self._zipped() if (side is None and nbr == 3 and grouping_mode() != 0) else None
-        if zipped is not None:
-            for pair in reversed(zipped):
-                yield [lambda op=op: bwd_op(op) for op in pair]
-            for op in rev:
-                if op.branch == 0:
-                    yield [lambda op=op: bwd_op(op)]
-        elif side is not None:
-            side.wait_stream(cur_stream)
-            sb = side_branch()
-            defer_on[0] = need_wgrad and defer_decoder_wgrad()
-            with torch.cuda.stream(side):
-                for op in rev:
-                    if op.branch != 0 and (op.branch >= 2) == (sb == 2):
-                        bwd_op(op)
-            for op in rev:
-                if op.branch != 0 and (op.branch >= 2) != (sb == 2):
-                    bwd_op(op)
-            defer_on[0] = False
-            if deferred:
-                # join the CHAINS only; the deferred weight gradients follow on the forked stream (they read gradient tensors of both decoders) and are
-                # joined at the end of the pass
-                chain_done = torch.cuda.Event()
-                chain_done.record(side)
-                main_done = torch.cuda.Event()
-                main_done.record(cur_stream)
-                cur_stream.wait_event(chain_done)
-                side.wait_event(main_done)
-                with torch.cuda.stream(side):
-                    for fn in deferred:
-                        fn()
-            else:
-                cur_stream.wait_stream(side)
-            for op in rev:
-                if op.branch == 0:
-                    bwd_op(op)
-            if deferred:
-                cur_stream.wait_stream(side)
-        else:
-            for op in rev:
-                yield [lambda op=op: bwd_op(op)]
-        return dx
+        # ---- schedule (pass_schedule): the decoders' backward passes in lockstep, on two streams or back to back, then the shared trunk
 
-    @staticmethod
-    def _scatter(contrib, op, srcs, dsrc, key=0):
-        if op.combine == 0:
-            off = 0
-            for name, s in zip(op.srcs, srcs):
-                contrib.setdefault(name, []).append((dsrc, off, key))
-                off += s.C
-        else:
-            for name in op.srcs:
-                contrib.setdefault(name, []).append((dsrc, 0, key))
+        def join():
+            if not deferred:
+                cur_stream.wait_stream(side)
+                return
+            # join the CHAINS only; the deferred weight gradients follow on the forked stream (they read gradient tensors of both decoders) and are
+            # joined at the end of the pass
+            chain_done = torch.cuda.Event()
+            chain_done.record(side)
+            main_done = torch.cuda.Event()
+            main_done.record(cur_stream)
+            cur_stream.wait_event(chain_done)
+            side.wait_event(main_done)
+            with torch.cuda.stream(side):
+                for fn in deferred:
+                    fn()
+        self._issue(self._schedule(mode, True), bwd_op, cur_stream, side, join)
+        if deferred:
+            cur_stream.wait_stream(side)
+        return dx
 
 
 class Rng:

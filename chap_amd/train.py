@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .engine import switch
 
 
 def sigmoid_rampup(current, rampup_length):
@@ -91,6 +92,13 @@ def check_graph_environment(concurrent=True, environ=None):
                         "aborts in the runtime below that).  Unset GPU_MAX_HW_QUEUES (default 4) or build the step with args={'concurrent': False}." % n)
 
 
+# The passes on a capture's origin stream that may fork their second decoder onto a stream of its own, as the bits of CHAP_FORK_MASK (engine.SWITCHES)
+FORK_PASS_A = 1                 # pass A
+FORK_POWER_BACKWARD = 2         # the power iteration's backward to the input
+FORK_VAT_FORWARD = 4            # the VAT forward passes after the first
+FORK_FINAL_BACKWARD = 8         # the final VAT backward
+
+
 class VAT2d:
     """adv_loss = VAT2d(xi, epi, num_classes); adv_loss(model, x, soft1, soft2, mask, losstype)
     (call sites train_ours_2D.py:290,372); losstype 'kl' or 'dice' (--adv_losstype, :515), `sign=True` = the FGSM-style
@@ -122,62 +130,49 @@ class VAT2d:
                 first = model(xh, update_stats=False, drop_masks=inject.get("drop_V0"))
         return dict(x=x, d=d, xh=xh, first=first, inject=inject)
 
-    def finish(self, model, st, soft1, soft2, mask, losstype="kl", weight_dev=None, accumulate_grad=True, grad_buffer=None, weight=1.0, fork_ctl=None):
-        gen = self.finish_steps(model, st, soft1, soft2, mask, losstype, weight_dev, accumulate_grad, grad_buffer, weight, fork_ctl)
-        while True:
-            try:
-                next(gen)
-            except StopIteration as e:
-                return e.value
-
-    def finish_steps(self, model, st, soft1, soft2, mask, losstype="kl", weight_dev=None, accumulate_grad=True, grad_buffer=None, weight=1.0, fork_ctl=None):
-        """finish() as a generator that yields between its passes -- [power iteration k: distance gradient, backward to the input, normalise] ...,
-        [final forward + distance], [final backward] -- so that the caller can ISSUE another chain's passes in between (ChapStep._iteration: the order
-        in which the nodes of a captured graph were created is the order in which a replay feeds them to the GPU, see there).  Returns the loss."""
+    def finish(self, model, st, soft1, soft2, mask, losstype="kl", weight_dev=None, accumulate_grad=True, grad_buffer=None, weight=1.0, forks=None):
+        """The rest of the VAT computation, pass by pass: [power iteration k: distance gradient, backward to the input, normalise] ..., the final forward +
+        distance, the final backward.  `forks(bit)` (ChapStep._forks; default: nothing) is entered around every pass: which of them fork their second
+        decoder under capture (FORK_*, CHAP_FORK_MASK).  Returns the loss."""
         if losstype not in ops.DIST_MODES:
             raise ValueError("chap_amd VAT2d: adv_losstype=%r (--adv_losstype {kl,dice}, train_ours_2D.py:515)" % (losstype,))
+        forks = forks or (lambda bit: contextlib.nullcontext())
         x, d, xh, inject = st["x"], st["d"], st["xh"], st["inject"]
-        fork_ctl = fork_ctl or (lambda bit: None)      # (ChapStep: which passes of the chain may fork their second decoder under capture, CHAP_FORK_MASK)
         for it in range(self.ip):
             if it == 0:
                 l1, l2 = st["first"]
             else:
                 ops.perturb(x, d, xh, self.xi)
-                fork_ctl(4)
-                with model.frozen():
+                with forks(FORK_VAT_FORWARD), model.frozen():
                     l1, l2 = model(xh, update_stats=False, drop_masks=inject.get("drop_V%d" % it))
             g1, g2 = torch.empty_like(l1), torch.empty_like(l2)
             ops.kl_fwd_bwd((l1, l2), (soft1, soft2), None, (g1, g2), mode=losstype)
-            fork_ctl(2)
             # d(distance)/d(x) only (the weights are frozen: no weight-gradient kernels), on the CURRENT stream whatever stream the
             # forward ran on (torch.autograd would run the node on the forward's stream)
-            dx = model.backward_saved(l1, [g1, g2], need_wgrad=False, need_dx=True)
+            with forks(FORK_POWER_BACKWARD):
+                dx = model.backward_saved(l1, [g1, g2], need_wgrad=False, need_dx=True)
             model.release_saved(l1)
             ops.l2_normalize(dx, d)
-            yield
         xa = torch.empty_like(x)
         m = None if mask is None else mask.reshape(x.shape)
         alpha = self.epi / math.sqrt(x[0].numel()) if self.sign else self.epi
         ops.perturb(x, d, xa, alpha, mask=m, sign=self.sign)
         loss = torch.zeros(1, dtype=torch.float32, device=x.device)
         if accumulate_grad:
-            fork_ctl(4)
-            l1, l2 = model(xa, update_stats=False, drop_masks=inject.get("drop_VF"), grad_buffer=grad_buffer)
+            with forks(FORK_VAT_FORWARD):
+                l1, l2 = model(xa, update_stats=False, drop_masks=inject.get("drop_VF"), grad_buffer=grad_buffer)
             g1, g2 = torch.empty_like(l1), torch.empty_like(l2)
             ops.kl_fwd_bwd((l1, l2), (soft1, soft2), loss, (g1, g2), gscale=weight, gscale_dev=weight_dev, mode=losstype)
-            yield
-            fork_ctl(8)
-            torch.autograd.backward([l1, l2], [g1, g2])
+            with forks(FORK_FINAL_BACKWARD):
+                torch.autograd.backward([l1, l2], [g1, g2])
         else:
-            with torch.no_grad():
+            with forks(FORK_VAT_FORWARD), torch.no_grad():
                 l1, l2 = model(xa, update_stats=False, drop_masks=inject.get("drop_VF"))
             ops.kl_fwd_bwd((l1, l2), (soft1, soft2), loss, mode=losstype)
         return loss
 
     def __call__(self, model, x, soft1, soft2, mask, losstype="kl", weight_dev=None, inject=None, accumulate_grad=True, grad_buffer=None,
                  weight=1.0):
-        if losstype not in ops.DIST_MODES:
-            raise ValueError("chap_amd VAT2d: adv_losstype=%r (--adv_losstype {kl,dice}, train_ours_2D.py:515)" % (losstype,))
         st = self.begin(model, x, soft1.shape[0], inject)
         return self.finish(model, st, soft1, soft2, mask, losstype, weight_dev, accumulate_grad, grad_buffer, weight)
 
@@ -289,6 +284,8 @@ class ChapStep:
         # goes to the side stream with its decoders back to back.
         self._d2 = st[1] if self.concurrent else None
         self._pre = st[2] if self.concurrent else None              # the VAT pre-pass beside pass A
+        self._fork_sides, self._fork_mask = {}, 0                   # inside _decoder_fork under capture: {origin stream: forked stream}, CHAP_FORK_MASK
+        self._stage_v, self._staged = None, False                   # stage() / stage_from(): made at the first call; a staged batch waits for replay()
 
     # ------------------------------------------------------------------ host-side schedule values
     def prepare(self, box_yx=None):
@@ -383,50 +380,51 @@ class ChapStep:
                 # ROCm 7.2 graph executor places the chains of a captured graph on its hardware queues by the creation order of the nodes, and in that
                 # order pass B lands on the VAT chain's queue and runs entirely after it ("Issue order").
                 self._side.wait_stream(main)
-                with torch.cuda.stream(self._side):
+                with torch.cuda.stream(self._side):      # (not the capture's origin stream: pass B's decoders never fork there)
                     losses = self._phase_b(ctx)
                     if self.grad_sync is not None and update and not torch.cuda.is_current_stream_capturing():
                         self.grad_sync.start_first()        # bucket 0 is final: its all-reduce runs beside the VAT chain
                 vat_loss = self._phase_v(ctx)
                 main.wait_stream(self._side)
             else:
-                losses = self._phase_b(ctx)
+                with self._forks(FORK_PASS_A):          # pass B on this (the origin) stream forks as pass A does
+                    losses = self._phase_b(ctx)
                 vat_loss = self._phase_v(ctx)
         out = {"mix_losses": losses, "vat_loss": vat_loss}
-        if self.args["dropout"]:
+        if self.args["dropout"]:        # (behind _decoder_fork's join: the fp branch never forks its second decoder under capture)
             out["fp_losses"] = self._fp_branch(ctx["uimg_ab"], ctx["pseudo_outputs1"], ctx["pseudo_outputs2"], ctx["inject"], None)
         if update:
             self.exchange_and_update()
         return out
 
-    def _fork_ctl(self, bit):
-        """CHAP_FORK_MASK (lab / A-B switch, default 14): which passes of the capture's origin stream fork their second decoder onto a stream of its own
-        (1 pass A, 2 the power iteration's backward, 4 the VAT forward passes after the first, 8 the final backward); the others run their decoders with
-        grouped launches.  Every fork is one more chain for the graph executor to place on its few hardware queues ("Issue order").
-        Round 4, 12 masks on the whole iteration (profiles/r04_issue_order_ab.log): 14 -- pass A, which already shares the GPU with the early VAT pass,
-        keeps its decoders on one stream -- 6.469 ms against 6.513 for 15 (three pairs; 3D 14.79 vs 14.81), every other mask slower (0: 6.83 / 15.8)."""
-        cs = getattr(self, "_cs_active", None)
-        if cs is None:
-            return
-        mask = int(os.environ.get("CHAP_FORK_MASK", "14"))
-        self.model._exec._capture_sides = cs if (mask & bit) else {}
-
     @contextlib.contextmanager
     def _decoder_fork(self, origin):
-        """Under capture: let the executor run the second decoder of the passes on `origin` on a stream forked from it (a
-        captured stream may fork / join with the capture's ORIGIN stream only, see __init__)."""
+        """Under capture: the passes on `origin` inside may run their second decoder on a stream forked from it (a captured stream may fork / join
+        with the capture's ORIGIN stream only, see __init__); which of them do is decided pass by pass (_forks) against CHAP_FORK_MASK, read here
+        once per captured iteration."""
         capturing = self.concurrent and torch.cuda.is_current_stream_capturing()
         if capturing:
             self._d2.wait_stream(origin)
-            self._cs_active = {origin.cuda_stream: self._d2}
-            self.model._exec._capture_sides = self._cs_active
+            self._fork_sides, self._fork_mask = {origin.cuda_stream: self._d2}, switch("CHAP_FORK_MASK")
         try:
             yield
         finally:
             if capturing:
                 origin.wait_stream(self._d2)
-                self.model._exec._capture_sides = {}
-                self._cs_active = None
+                self._fork_sides = {}
+
+    @contextlib.contextmanager
+    def _forks(self, bit=None):
+        """Around one pass (a forward or a backward of the model) on the capture's origin stream: inside, the executor forks the pass's second decoder
+        if CHAP_FORK_MASK has `bit` (FORK_*; None: regardless of the mask) -- that is, Executor._side_stream answers with _decoder_fork's stream -- and
+        groups the two decoders' launches otherwise.  Outside _decoder_fork (eager, single-stream step) it changes nothing."""
+        ex = self.model._exec
+        old = ex._capture_sides
+        ex._capture_sides = self._fork_sides if (bit is None or self._fork_mask & bit) else {}
+        try:
+            yield
+        finally:
+            ex._capture_sides = old
 
     def _phase_a(self, volume_batch, label_batch, inject):
         a, model = self.args, self.model
@@ -452,10 +450,10 @@ class ChapStep:
                 with torch.enable_grad(), torch.cuda.stream(pre):
                     ctx["vat_state"] = self.adv_loss.begin(model, volume_batch, B - lbs, inject)
             else:
-                ctx["vat_state"] = self.adv_loss.begin(model, volume_batch, B - lbs, inject)
+                with self._forks():                 # the first VAT forward on this (the origin) stream forks whatever the mask says
+                    ctx["vat_state"] = self.adv_loss.begin(model, volume_batch, B - lbs, inject)
         # ---- pass A: pseudo labels from both decoders (no grad), train_ours_2D.py:314-330
-        self._fork_ctl(1)
-        with torch.no_grad():
+        with self._forks(FORK_PASS_A), torch.no_grad():
             pre_ab1, pre_ab2 = model(ctx["uimg_ab"], drop_masks=inject.get("drop_A"))
             soft1, soft2, pseudo1, pseudo2, knowledge = ops.pseudo_block(pre_ab1, pre_ab2)
         if pre is not None:
@@ -467,24 +465,10 @@ class ChapStep:
             ctx["diff_mask"] = ops.diff_mask(pseudo1, pseudo2, knowledge, 4, a["topk1"])
         return ctx
 
-    @staticmethod
-    def _drain(gen):
-        while True:
-            try:
-                next(gen)
-            except StopIteration as e:
-                return e.value
-
     def _phase_b(self, ctx):
-        return self._drain(self._phase_b_steps(ctx))
-
-    def _phase_v(self, ctx):
-        return self._drain(self._phase_v_steps(ctx))
-
-    def _phase_b_steps(self, ctx):
         """Largest-CC filter, loss mask and BCP mixing (:326-338) feed pass B only: they run at the head of this branch, off
         the critical path (the VAT branch needs the soft / arg-max outputs, not these); then pass B and the four mix_loss
-        terms (:339-351), backward into gradient bucket 0.  A generator: yields between its forward and its backward part (see _iteration)."""
+        terms (:339-351), backward into gradient bucket 0."""
         a, model, inject = self.args, self.model, ctx["inject"]
         nc = a["num_classes"]
         lsub, usub, volume_batch = ctx["lsub"], ctx["usub"], ctx["volume_batch"]
@@ -547,7 +531,6 @@ class ChapStep:
             else:
                 ops.mix_loss_bwd(lg, img_l, patch_l, loss_mask, iw, pw, acc, dl)
             losses.append(loss3)
-        yield
         if not split:
             torch.autograd.backward([out_mix1, out_mix2], [d1, d2])
             return losses
@@ -566,12 +549,12 @@ class ChapStep:
         ops.perturb(b0, g_u, b0, 1.0)
         return losses
 
-    def _phase_v_steps(self, ctx):
+    def _phase_v(self, ctx):
         a = self.args
         if not a["adv_noise"]:
             return torch.zeros(1, dtype=torch.float32, device=ctx["volume_batch"].device)
-        return (yield from self.adv_loss.finish_steps(self.model, ctx["vat_state"], ctx["outputs_soft1"], ctx["outputs_soft2"], ctx["diff_mask"], a["adv_losstype"],
-                                                      weight_dev=self.cw_dev, grad_buffer=self.grad2, fork_ctl=self._fork_ctl))
+        return self.adv_loss.finish(self.model, ctx["vat_state"], ctx["outputs_soft1"], ctx["outputs_soft2"], ctx["diff_mask"], a["adv_losstype"],
+                                    weight_dev=self.cw_dev, grad_buffer=self.grad2, forks=self._forks)
 
     def _fp_branch(self, uimg_ab, pseudo1, pseudo2, inject, capturing):
         """"2) fp" of the loop (train_ours_2D.py:359-365, default off): both decoders on the channel-perturbed features
@@ -681,13 +664,13 @@ class ChapStep:
             with self._decoder_fork(torch.cuda.current_stream()):
                 ctx = self._phase_a(self._static_v, self._static_l, inject)
         with torch.cuda.graph(gB, **kw):
-            with self._decoder_fork(torch.cuda.current_stream()):
+            with self._decoder_fork(torch.cuda.current_stream()), self._forks():      # graph B's pass B forks whatever the mask says
                 losses = self._phase_b(ctx)
         with torch.cuda.graph(gV, **kw):
             with self._decoder_fork(torch.cuda.current_stream()):
                 vat_loss = self._phase_v(ctx)
             out = {"mix_losses": losses, "vat_loss": vat_loss}
-            if self.args["dropout"]:
+            if self.args["dropout"]:    # (behind _decoder_fork's join, as in _iteration: no fork)
                 out["fp_losses"] = self._fp_branch(ctx["uimg_ab"], ctx["pseudo_outputs1"], ctx["pseudo_outputs2"], ctx["inject"], None)
         stack.close()
         with torch.cuda.graph(gO, **kw):
@@ -696,41 +679,38 @@ class ChapStep:
         self._graph, self._graph_opt, self._graphs_dp = None, None, (gA, gB, gV, gO)
         return gA
 
+    def _stage(self, fill):
+        """fill(image_out, label_out) on the copy stream, into the staging buffers, behind the hand-over of the batch staged before."""
+        if self._stage_v is None:
+            self._stage_v, self._stage_l = torch.empty_like(self._static_v), torch.empty_like(self._static_l)
+            self._copy_stream = torch.cuda.Stream(device=self._static_v.device)
+            self._staged_evt, self._taken_evt = torch.cuda.Event(), None
+        with torch.cuda.stream(self._copy_stream):
+            if self._taken_evt is not None:
+                self._copy_stream.wait_event(self._taken_evt)      # the previous staged batch has been moved into the static buffers
+            fill(self._stage_v, self._stage_l)
+            self._staged_evt.record(self._copy_stream)
+        self._staged = True
+
     def stage(self, volume_batch, label_batch):
         """Start the host-to-device copy of the NEXT batch on a copy stream, beside the iteration that is running: the loader of
         train_ours_2D.py:301-304 yields CPU tensors and `.cuda()`s them on the compute stream (19 MB per 2D iteration, 0.4 ms of PCIe time in front
         of every step; 3D 1.0 ms).  replay() without a batch then takes the staged one (a device-to-device copy of microseconds).  Pinned source
         tensors make the copy asynchronous to the host as well."""
-        if getattr(self, "_stage_v", None) is None:
-            self._stage_v, self._stage_l = torch.empty_like(self._static_v), torch.empty_like(self._static_l)
-            self._copy_stream = torch.cuda.Stream(device=self._static_v.device)
-            self._staged_evt, self._taken_evt = torch.cuda.Event(), None
-        with torch.cuda.stream(self._copy_stream):
-            if self._taken_evt is not None:
-                self._copy_stream.wait_event(self._taken_evt)      # the previous staged batch has been moved into the static buffers
-            self._stage_v.copy_(volume_batch, non_blocking=True)
-            self._stage_l.copy_(label_batch, non_blocking=True)
-            self._staged_evt.record(self._copy_stream)
-        self._staged = True
+        def fill(image_out, label_out):
+            image_out.copy_(volume_batch, non_blocking=True)
+            label_out.copy_(label_batch, non_blocking=True)
+        self._stage(fill)
 
     def stage_from(self, loader):
         """stage() for a device-resident loader (chap_amd.data.DeviceLoader): instead of a host-to-device copy, the copy stream runs the
         loader's augmentation kernel straight into the staging buffers -- `loader.next_into(image_out, label_out)` launches on the current
         stream -- so the batch of iteration n + 1 is built beside iteration n and replay() takes it as it takes any staged batch."""
-        if getattr(self, "_stage_v", None) is None:
-            self._stage_v, self._stage_l = torch.empty_like(self._static_v), torch.empty_like(self._static_l)
-            self._copy_stream = torch.cuda.Stream(device=self._static_v.device)
-            self._staged_evt, self._taken_evt = torch.cuda.Event(), None
-        with torch.cuda.stream(self._copy_stream):
-            if self._taken_evt is not None:
-                self._copy_stream.wait_event(self._taken_evt)      # the previous staged batch has been moved into the static buffers
-            loader.next_into(self._stage_v, self._stage_l)
-            self._staged_evt.record(self._copy_stream)
-        self._staged = True
+        self._stage(loader.next_into)
 
     def replay(self, volume_batch=None, label_batch=None, box_yx=None):
         if volume_batch is None:
-            if not getattr(self, "_staged", False):
+            if not self._staged:
                 raise RuntimeError("chap_amd: replay() without a batch needs a stage()d one")
             main = torch.cuda.current_stream()
             main.wait_event(self._staged_evt)
