@@ -123,18 +123,9 @@ __device__ __forceinline__ void conv_c1_mfma_kernel(const chap_conv_c1_params& P
             if (valid) st4((T*)P.out + ((((long)n * P.D + z) * P.H + y) * P.W + x) * 16 + 4 * g, o);
         }
     }
-    if (do_stats) {      // registers -> 16-lane DPP reduce -> LDS row of this wave -> the four rows in a fixed order -> this block's partial slot
+    if (do_stats) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float s = row16_sum(ssum[j]), q = row16_sum(ssq[j]);
-            if (px == 0) { bstat[(wave * 2 + 0) * 16 + 4 * g + j] = s; bstat[(wave * 2 + 1) * 16 + 4 * g + j] = q; }
-        }
-        __syncthreads();
-        if (blockIdx.x == 0 && threadIdx.x == 0) *(int*)P.stats = (int)gridDim.x;      // header: slots in use
-        float* st = P.stats + CHAP_STATS_HDR + (long)blockIdx.x * 2 * 16;
-        if (threadIdx.x < 32) {
-            const int which = threadIdx.x >> 4, c = threadIdx.x & 15;
-            st[which * 16 + c] = (bstat[(0 * 2 + which) * 16 + c] + bstat[(1 * 2 + which) * 16 + c]) + (bstat[(2 * 2 + which) * 16 + c] + bstat[(3 * 2 + which) * 16 + c]);
-        }
+        for (int j = 0; j < 4; ++j) conv_stats_row<1>(bstat, 0, j, ssum[j], ssq[j], wave, g, px);
+        conv_stats_flush<1>(bstat, P.stats, 16, 0);
     }
 }

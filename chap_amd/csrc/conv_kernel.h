@@ -16,6 +16,7 @@
 #pragma once
 #include "common.h"
 #include "launch.h"
+#include "conv_parts.h"
 #include <type_traits>
 
 #ifndef CHAP_CONV_MINWAVES
@@ -144,9 +145,6 @@ template <typename T, int UNITS, bool ADD2, bool KEEPM = true> struct halo_regs 
     unsigned ok;               // bit j: unit j is inside the input (else zero padding)
 };
 
-constexpr int UNIT_UNUSED = 511 << 20;                          // z field beyond any halo: never inside
-constexpr unsigned UNIT_GUARD = (1u << 29) | (1u << 19) | (1u << 9);
-
 template <int UNITS> struct unit_desc {
     int hzyx[UNITS];           // hz << 20 | hy << 10 | hx   (UNIT_UNUSED: this thread has no such unit; only the last can be)
     int rel[UNITS];            // (hz*IH + hy)*IW + hx : input pixel offset from the halo origin
@@ -188,12 +186,8 @@ __device__ __forceinline__ src_scalars make_scalars(const chap_src_t& s) {
 template <typename T, typename G, bool D3, int ST, int KC, bool ADD2, int UNITS, bool LANESEL, bool ONE>
 __device__ __forceinline__ void halo_issue_impl(halo_regs<T, UNITS, ADD2, !D3>& R, const unit_desc<UNITS>& U, const src_scalars& s0, const src_scalars& s1,
                                                 int ID, int IH, int IW, int n, int z0, int y0, int x0, int chunk) {
-    const int gz0 = z0 * G::STD - (D3 ? G::PAD : 0), gy0 = y0 * ST - G::PAD, gx0 = x0 * ST - G::PAD;
-    const long gp0 = (((long)n * ID + gz0) * IH + gy0) * IW + gx0;           // halo origin (may lie outside: only offsets that pass the bounds test are used)
-    const int loz = max(0, -gz0), hiz = min(G::HD, ID - gz0), loy = max(0, -gy0), hiy = min(G::HH, IH - gy0), lox = max(0, -gx0), hix = min(G::HW, IW - gx0);
-    const unsigned PA = ((unsigned)(512 - loz) << 20) | ((unsigned)(512 - loy) << 10) | (unsigned)(512 - lox);
-    const unsigned PB = ((unsigned)(512 - hiz) << 20) | ((unsigned)(512 - hiy) << 10) | (unsigned)(512 - hix);
-    const unsigned rsafe = ((D3 ? G::PAD : 0) * IH + G::PAD) * IW + G::PAD;
+    const halo_bounds_t B = halo_bounds<G, D3, ST>(ID, IH, IW, n, z0, y0, x0);
+    const long gp0 = B.gp0;
     const int cb = chunk * KC;
     const bool second = (ADD2 || ONE) ? false : (LANESEL ? (cb + U.c8 >= s0.C) : (cb >= s0.C));
     const int cs = second ? cb - s0.C : cb;                      // first channel of the chunk inside the source (can be < 0 for LANESEL lanes of s1: + c8 >= 0)
@@ -206,10 +200,9 @@ __device__ __forceinline__ void halo_issue_impl(halo_regs<T, UNITS, ADD2, !D3>& 
     unsigned okm = 0, r[UNITS];
 #pragma unroll
     for (int j = 0; j < UNITS; ++j) {
-        const unsigned d = (unsigned)U.hzyx[j];
-        const bool ok = (((d + PA) ^ (d + PB)) & UNIT_GUARD) == UNIT_GUARD;
+        const bool ok = B.inside(U.hzyx[j]);
         okm |= ok ? (1u << j) : 0u;
-        r[j] = ok ? (unsigned)U.rel[j] : rsafe;
+        r[j] = ok ? (unsigned)U.rel[j] : B.rsafe;
     }
     R.ok = okm;
     if (CHAP_ABLATE & 16) return;
@@ -410,8 +403,7 @@ __device__ __forceinline__ void conv_fwd_kernel(const chap_conv_params& P) {
     const int Ctot = P.combine == 0 ? (P.src[0].C + (P.nsrc > 1 ? P.src[1].C : 0)) : P.src[0].C;
     const int nchunks = Ctot / KC;
     const bool plain = (CHAP_ABLATE & 4) ||
-                       (!ADD2 && P.src[0].scale == nullptr && !P.src[0].act && P.src[0].keep == nullptr && P.src[0].chan_mul == nullptr &&
-                        (P.nsrc < 2 || (P.src[1].scale == nullptr && !P.src[1].act && P.src[1].keep == nullptr && P.src[1].chan_mul == nullptr)));
+                       (!ADD2 && src_is_plain(P.src[0]) && (P.nsrc < 2 || src_is_plain(P.src[1])));
     const src_scalars s0 = make_scalars(P.src[0]);
     const src_scalars s1 = make_scalars((!ONE && P.nsrc > 1) ? P.src[1] : P.src[0]);
 
@@ -444,7 +436,7 @@ __device__ __forceinline__ void conv_fwd_kernel(const chap_conv_params& P) {
     unit_desc<UNITS> U;
     make_units<G, GPT, PS, UNITS>(U, P.IH, P.IW);
     const bool lanesel = !ADD2 && !ONE && P.nsrc > 1 && (P.src[0].C % KC) != 0;   // a K-chunk straddles the two concatenated sources
-    int xoff[STEPS];                                            // LDS element offset of this lane's B fragment (row m = 0), -1 = zero fragment
+    int xoff[STEPS];                                            // LDS element offset of this lane's B fragment (row m = 0), -1 = zero fragment (load_xfrag)
 #pragma unroll
     for (int step = 0; step < STEPS; ++step) {
         const int p = step * 4 + g;
@@ -616,7 +608,7 @@ __device__ __forceinline__ void conv_fwd_kernel(const chap_conv_params& P) {
                 const int sx = sub & 1, sy = (sub >> 1) & 1, sz = (sub >> 2) & 1;
                 ooff[t] = (((sz * OH) + sy) * OW + 2 * px + sx) * P.out_ld + P.out_coff + oc;
             } else {
-                ooff[t] = px * P.out_ld + P.out_coff + ((P.out2 && nl >= P.out2_from) ? nl - P.out2_from : nl);      // (out2: the upper channel tiles land in a second dense tensor)
+                ooff[t] = cl_out_offset(P, nl, px);
             }
         }
         orow = P.out_planar ? P.W : (P.out_mode == 1 ? 2 * OW * P.out_ld : P.W * P.out_ld);
@@ -679,12 +671,8 @@ __device__ __forceinline__ void conv_fwd_kernel(const chap_conv_params& P) {
             }
         };
         auto load_x = [&](int step, F (&xf)[MR]) {
-            const int xo = xoff[step];
 #pragma unroll
-            for (int m = 0; m < MR; ++m) {
-                if (step * 4 + 3 < NP) xf[m] = frag<T>::load(cur + xo + m * (ST * G::HW * PS));        // every lane group has a tap
-                else xf[m] = xo >= 0 ? frag<T>::load(cur + xo + m * (ST * G::HW * PS)) : frag<T>::zero();
-            }
+            for (int m = 0; m < MR; ++m) xf[m] = load_xfrag<T, NP>(cur, xoff[step], m * (ST * G::HW * PS), step);
         };
         // pixel fragments (LDS) one step ahead; weight fragments one step ahead from LDS, TWO steps ahead when they
         // stream from L2 (one step of MR*NT MFMAs does not cover an L2 round trip)
@@ -807,10 +795,8 @@ __device__ __forceinline__ void conv_fwd_kernel(const chap_conv_params& P) {
     }
 
     CHAP_STAMP_P(4);
-    // ---- BatchNorm statistics: registers -> 16-lane DPP reduce -> LDS row of this wave -> the four rows summed in a fixed
-    // order -> this block's partial slot (plain stores: no atomics anywhere, chap_bn_finalize sums the slots in a fixed
-    // order, so the statistics are bitwise reproducible for a given launch geometry)
     if (do_stats) {
+        // (the wave's row, conv_stats_row's layout, written in place: through the function the register allocation of some instances moves)
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
 #pragma unroll
@@ -822,15 +808,7 @@ __device__ __forceinline__ void conv_fwd_kernel(const chap_conv_params& P) {
                 }
             }
         }
-        __syncthreads();
-        if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *(int*)P.stats = (int)gridDim.x;      // header: slots in use
-        float* st = P.stats + CHAP_STATS_HDR + (long)blockIdx.x * 2 * P.Cout;      // slot rows are indexed by the LOGICAL channel (a transposed conv's sub-lattices are folded by the finalize)
-        for (int i = threadIdx.x; i < 2 * 16 * NT; i += 256) {
-            const int which = i / (16 * NT), k = i % (16 * NT);
-            const int nl = nt0 * 16 + k;
-            const float v = (bstat[(0 * 2 + which) * 16 * NT + k] + bstat[(1 * 2 + which) * 16 * NT + k]) + (bstat[(2 * 2 + which) * 16 * NT + k] + bstat[(3 * 2 + which) * 16 * NT + k]);
-            if (nl < P.Cout) st[which * P.Cout + nl] = v;
-        }
+        conv_stats_flush<NT>(bstat, P.stats, P.Cout, nt0);
     }
     CHAP_STAMP_P(5);
 }

@@ -10,9 +10,9 @@
 // A tile costs one memory round trip + one tap loop per ROUND of CPAR chunks instead of one per chunk.
 //
 // Same operands, packed-weight layout, lazy-activation prologue (BN affine, LeakyReLU, Dropout keep masks, Dropout3d channel
-// multipliers, two concatenated sources), statistics slots and bit-level output conventions as conv_fwd_kernel; built for the
-// plain channel-last output (no depth-to-space, no planar logits, no skip add) -- conv_make_plan (conv_plan.h) routes everything else to
-// conv_fwd_kernel.
+// multipliers, two concatenated sources) as conv_fwd_kernel, statistics slots by conv_stats_row / conv_stats_flush and output offsets by
+// cl_out_offset (conv_parts.h), so the same bits; built for the plain channel-last output (no depth-to-space, no planar logits, no skip
+// add) -- conv_make_plan (conv_plan.h) routes everything else to conv_fwd_kernel.
 #pragma once
 #include "conv_kernel.h"
 
@@ -58,8 +58,7 @@ __device__ __forceinline__ void conv_kpar_kernel(const chap_conv_params& P) {   
     const int nt0 = blockIdx.y * NT;
     const int Ctot = P.src[0].C + ((!ONE && P.nsrc > 1) ? P.src[1].C : 0);
     const int nrounds = Ctot / (KC * CPAR);
-    const bool plain = P.src[0].scale == nullptr && !P.src[0].act && P.src[0].keep == nullptr && P.src[0].chan_mul == nullptr &&
-                       (ONE || P.nsrc < 2 || (P.src[1].scale == nullptr && !P.src[1].act && P.src[1].keep == nullptr && P.src[1].chan_mul == nullptr));
+    const bool plain = src_is_plain(P.src[0]) && (ONE || P.nsrc < 2 || src_is_plain(P.src[1]));
     const src_scalars s0 = make_scalars(P.src[0]);
     const src_scalars s1 = make_scalars((!ONE && P.nsrc > 1) ? P.src[1] : P.src[0]);
     const bool do_stats = P.stats != nullptr;
@@ -67,7 +66,7 @@ __device__ __forceinline__ void conv_kpar_kernel(const chap_conv_params& P) {   
     // ---- one-time per thread
     unit_desc<UNITS> U;
     make_units<G, GPT, PS, UNITS>(U, P.IH, P.IW);
-    int xoff[STEPS];                                            // LDS element offset of this lane's pixel fragment (row 0), -1 = zero fragment
+    int xoff[STEPS];                                            // LDS element offset of this lane's pixel fragment (row 0), -1 = zero fragment (load_xfrag)
 #pragma unroll
     for (int step = 0; step < STEPS; ++step) {
         const int p = step * 4 + g;
@@ -76,18 +75,9 @@ __device__ __forceinline__ void conv_kpar_kernel(const chap_conv_params& P) {   
         xoff[step] = p < NP ? ((dz * G::HH + dy) * G::HW + px + dx) * PS + cgl * 8 : -1;
     }
     const int ck = wave % CPAR, rgrp = wave / CPAR;             // this wave's chunk of a round, its row group in the tap loop
-    // scale/shift of both sources -> LDS cache (conv_fwd_kernel's layout)
     if (!plain) {
-        for (int s = 0; s < (ONE ? 1 : 2); ++s) {
-            if (s < P.nsrc) {
-                const chap_src_t& S = P.src[s];
-                const bool has = S.scale != nullptr;
-                for (int c = threadIdx.x; c < S.C && c < CONV_MAX_AFFINE_C / 2; c += 256) {
-                    aff[s * CONV_MAX_AFFINE_C + c] = has ? S.scale[c] : 1.f;
-                    aff[s * CONV_MAX_AFFINE_C + CONV_MAX_AFFINE_C / 2 + c] = has ? S.shift[c] : 0.f;
-                }
-            }
-        }
+        for (int s = 0; s < (ONE ? 1 : 2); ++s)
+            if (s < P.nsrc) aff_cache_fill<CONV_MAX_AFFINE_C>(aff + s * CONV_MAX_AFFINE_C, P.src[s]);
     }
     float ssum[NT][4], ssq[NT][4], bj[NT][4], cj[NT][4];
     {
@@ -107,7 +97,7 @@ __device__ __forceinline__ void conv_kpar_kernel(const chap_conv_params& P) {   
     const int orow = P.W * P.out_ld;
     int ooff[NT];
 #pragma unroll
-    for (int t = 0; t < NT; ++t) ooff[t] = px * P.out_ld + P.out_coff + (nt0 + t) * 16 + 4 * g;
+    for (int t = 0; t < NT; ++t) ooff[t] = cl_out_offset(P, (nt0 + t) * 16 + 4 * g, px);
 
     CHAP_KSTAMP(1);
     for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
@@ -142,12 +132,8 @@ __device__ __forceinline__ void conv_kpar_kernel(const chap_conv_params& P) {   
             // ---- tap loop of chunk r*CPAR + ck over this wave's RW rows; weight fragments stream from L2 two steps ahead
             const T* hb = halo + ck * HB + (size_t)(rgrp * RW) * (ST * G::HW * PS);
             auto load_x = [&](int step, F (&xf)[RW]) __attribute__((always_inline)) {
-                const int xo = xoff[step];
 #pragma unroll
-                for (int m = 0; m < RW; ++m) {
-                    if (step * 4 + 3 < NP) xf[m] = frag<T>::load(hb + xo + m * (ST * G::HW * PS));
-                    else xf[m] = xo >= 0 ? frag<T>::load(hb + xo + m * (ST * G::HW * PS)) : frag<T>::zero();
-                }
+                for (int m = 0; m < RW; ++m) xf[m] = load_xfrag<T, NP>(hb, xoff[step], m * (ST * G::HW * PS), step);
             };
             // ring depth of the weight fragments: a step is RW*NT MFMAs (16 cycles each), an L2 round trip ~700 cycles
             constexpr int WD0 = 2 + 700 / (RW * NT * 16), WD = WD0 > 8 ? 8 : (WD0 > STEPS ? STEPS : WD0);
@@ -206,29 +192,13 @@ __device__ __forceinline__ void conv_kpar_kernel(const chap_conv_params& P) {   
         }
     }
     CHAP_KSTAMP(9);
-    // ---- BatchNorm statistics: this block's partial slot (conv_fwd_kernel's layout and order)
     if (do_stats) {
-        __syncthreads();
+        __syncthreads();                                        // bstat follows the reduction buffer: every wave is through with it
 #pragma unroll
-        for (int t = 0; t < NT; ++t) {
+        for (int t = 0; t < NT; ++t)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float s = row16_sum(ssum[t][j]), q = row16_sum(ssq[t][j]);
-                if (px == 0) {
-                    bstat[(wave * 2 + 0) * 16 * NT + t * 16 + 4 * g + j] = s;
-                    bstat[(wave * 2 + 1) * 16 * NT + t * 16 + 4 * g + j] = q;
-                }
-            }
-        }
-        __syncthreads();
-        if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *(int*)P.stats = (int)gridDim.x;      // header: slots in use
-        float* st = P.stats + CHAP_STATS_HDR + (long)blockIdx.x * 2 * P.Cout;
-        for (int i = threadIdx.x; i < 2 * 16 * NT; i += 256) {
-            const int which = i / (16 * NT), k = i % (16 * NT);
-            const int nl = nt0 * 16 + k;
-            const float v = (bstat[(0 * 2 + which) * 16 * NT + k] + bstat[(1 * 2 + which) * 16 * NT + k]) + (bstat[(2 * 2 + which) * 16 * NT + k] + bstat[(3 * 2 + which) * 16 * NT + k]);
-            if (nl < P.Cout) st[which * P.Cout + nl] = v;
-        }
+            for (int j = 0; j < 4; ++j) conv_stats_row<NT>(bstat, t, j, ssum[t][j], ssq[t][j], wave, g, px);
+        conv_stats_flush<NT>(bstat, P.stats, P.Cout, nt0);
     }
     CHAP_KSTAMP(10);
 }

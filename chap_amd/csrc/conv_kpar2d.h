@@ -8,19 +8,14 @@
 template <typename T, typename G, bool D3, int ST, int KC, int UNITS, int CPAR, bool ONE, bool KEEPM>
 __device__ __forceinline__ void halo_issue_round(halo_regs<T, UNITS, false, KEEPM> (&R)[CPAR], const unit_desc<UNITS>& U, const src_scalars& s0, const src_scalars& s1,
                                                  int ID, int IH, int IW, int n, int z0, int y0, int x0, int chunk0) {
-    const int gz0 = z0 * G::STD - (D3 ? G::PAD : 0), gy0 = y0 * ST - G::PAD, gx0 = x0 * ST - G::PAD;
-    const long gp0 = (((long)n * ID + gz0) * IH + gy0) * IW + gx0;
-    const int loz = max(0, -gz0), hiz = min(G::HD, ID - gz0), loy = max(0, -gy0), hiy = min(G::HH, IH - gy0), lox = max(0, -gx0), hix = min(G::HW, IW - gx0);
-    const unsigned PA = ((unsigned)(512 - loz) << 20) | ((unsigned)(512 - loy) << 10) | (unsigned)(512 - lox);
-    const unsigned PB = ((unsigned)(512 - hiz) << 20) | ((unsigned)(512 - hiy) << 10) | (unsigned)(512 - hix);
-    const unsigned rsafe = ((D3 ? G::PAD : 0) * IH + G::PAD) * IW + G::PAD;
+    const halo_bounds_t B = halo_bounds<G, D3, ST>(ID, IH, IW, n, z0, y0, x0);
+    const long gp0 = B.gp0;
     unsigned okm = 0, r[UNITS];
 #pragma unroll
     for (int j = 0; j < UNITS; ++j) {
-        const unsigned d = (unsigned)U.hzyx[j];
-        const bool ok = (((d + PA) ^ (d + PB)) & UNIT_GUARD) == UNIT_GUARD;
+        const bool ok = B.inside(U.hzyx[j]);
         okm |= ok ? (1u << j) : 0u;
-        r[j] = ok ? (unsigned)U.rel[j] : rsafe;
+        r[j] = ok ? (unsigned)U.rel[j] : B.rsafe;
     }
     const unsigned lane_c = U.c8 * sizeof(T);
     unsigned off0[UNITS], off1[ONE ? 1 : UNITS];
@@ -65,7 +60,7 @@ __device__ __forceinline__ void halo_issue_round(halo_regs<T, UNITS, false, KEEP
 //     fragments per dx for 3 * RW MFMA rows -- 30 LDS reads per chunk instead of 72 (the loop was LDS-read bound at twice its MFMA time).
 // SINGLE (one round: <= 128 input channels): the accumulators are not live while the halos are staged, which is what leaves room for the weight
 // fragments beside them; layers with two rounds (256 channels) request each round's weight fragments behind its staging.
-// Same operands, statistics slots and output conventions as conv_kpar_kernel; conv_make_plan (conv_plan.h) routes (2D, k3 s1, 32-channel chunks, plain output).
+// Same operands, output conventions and finish as conv_kpar_kernel (bias and shift are masked at their use here), statistics slots: conv_stats_flush; conv_make_plan (conv_plan.h) routes (2D, k3 s1, 32-channel chunks, plain output).
 template <int NT, int CPAR, bool ONE, bool KEEPM, bool SINGLE>
 __device__ __forceinline__ void conv_kpar2d_kernel(const chap_conv_params& P) {      // runs behind chap_grouped<.., 256, 2> (launch.h)
     typedef bf16_t T;
@@ -95,8 +90,7 @@ __device__ __forceinline__ void conv_kpar2d_kernel(const chap_conv_params& P) { 
     const int nt0 = blockIdx.y * NT;
     const int Ctot = P.src[0].C + ((!ONE && P.nsrc > 1) ? P.src[1].C : 0);
     const int nrounds = SINGLE ? 1 : Ctot / (KC * CPAR);
-    const bool plain = P.src[0].scale == nullptr && !P.src[0].act && P.src[0].keep == nullptr && P.src[0].chan_mul == nullptr &&
-                       (ONE || P.nsrc < 2 || (P.src[1].scale == nullptr && !P.src[1].act && P.src[1].keep == nullptr && P.src[1].chan_mul == nullptr));
+    const bool plain = src_is_plain(P.src[0]) && (ONE || P.nsrc < 2 || src_is_plain(P.src[1]));
     const src_scalars s0 = make_scalars(P.src[0]);
     const src_scalars s1 = make_scalars((!ONE && P.nsrc > 1) ? P.src[1] : P.src[0]);
     const bool do_stats = P.stats != nullptr;
@@ -127,7 +121,7 @@ __device__ __forceinline__ void conv_kpar2d_kernel(const chap_conv_params& P) { 
     const int orow = P.W * P.out_ld;
     int ooff[NT];
 #pragma unroll
-    for (int t = 0; t < NT; ++t) ooff[t] = px * P.out_ld + P.out_coff + (nt0 + t) * 16 + 4 * g;
+    for (int t = 0; t < NT; ++t) ooff[t] = cl_out_offset(P, (nt0 + t) * 16 + 4 * g, px);
 
     CHAP_KSTAMP(1);
     bool first = true;
@@ -261,9 +255,9 @@ __device__ __forceinline__ void conv_kpar2d_kernel(const chap_conv_params& P) { 
         }
     }
     CHAP_KSTAMP(9);
-    // ---- BatchNorm statistics: this block's partial slot (conv_fwd_kernel's layout and order)
     if (do_stats) {
-        __syncthreads();
+        __syncthreads();                                        // bstat follows the reduction buffer: every wave is through with it
+        // (the wave's row, conv_stats_row's layout, written in place: through the function the register allocation of some instances moves)
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
 #pragma unroll
@@ -275,15 +269,7 @@ __device__ __forceinline__ void conv_kpar2d_kernel(const chap_conv_params& P) { 
                 }
             }
         }
-        __syncthreads();
-        if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *(int*)P.stats = (int)gridDim.x;      // header: slots in use
-        float* st = P.stats + CHAP_STATS_HDR + (long)blockIdx.x * 2 * P.Cout;
-        for (int i = threadIdx.x; i < 2 * 16 * NT; i += 256) {
-            const int which = i / (16 * NT), k = i % (16 * NT);
-            const int nl = nt0 * 16 + k;
-            const float v = (bstat[(0 * 2 + which) * 16 * NT + k] + bstat[(1 * 2 + which) * 16 * NT + k]) + (bstat[(2 * 2 + which) * 16 * NT + k] + bstat[(3 * 2 + which) * 16 * NT + k]);
-            if (nl < P.Cout) st[which * P.Cout + nl] = v;
-        }
+        conv_stats_flush<NT>(bstat, P.stats, P.Cout, nt0);
     }
     CHAP_KSTAMP(10);
 }

@@ -6,7 +6,7 @@
 // WAVE is its own pipeline: its own sequence of 4 x 16-pixel tiles, its own LDS halo region (single-buffered: a wave's LDS operations execute in
 // order) and its own register prefetch of the next tile; it computes all output channels of its tile from the block's weights, which sit in LDS once
 // per block (5-36 KB).  No block barrier in the tile loop; the four waves meet at the start (weights, scale / shift cache) and at the end (BatchNorm
-// statistics: the four waves' registers -> one partial slot per block, same layout and order as conv_fwd_kernel).
+// statistics: the four waves' registers -> one partial slot per block, conv_stats_flush).
 // Same operands, packed-weight layout, lazy-activation prologue (BN affine, LeakyReLU, keep masks, channel multipliers, two concatenated sources
 // inside the one chunk), bias, shifted statistics, channel-last output incl. out2; per output element the same MFMA sequence as conv_fwd_kernel
 // (K order: steps of the one chunk), so outputs are bit-identical to it; the statistics partials differ in how the pixels are dealt to slots.
@@ -50,24 +50,13 @@ __device__ __forceinline__ void conv_wp_kernel(const chap_conv_params& P) {
     const int ntiles_total = (P.Cout + 15) >> 4;
     const int nt0 = blockIdx.y * NT;
     const bool one = P.nsrc == 1;
-    const bool plain = P.src[0].scale == nullptr && !P.src[0].act && P.src[0].keep == nullptr && P.src[0].chan_mul == nullptr &&
-                       (one || (P.src[1].scale == nullptr && !P.src[1].act && P.src[1].keep == nullptr && P.src[1].chan_mul == nullptr));
+    const bool plain = src_is_plain(P.src[0]) && (one || src_is_plain(P.src[1]));
     const src_scalars s0 = make_scalars(P.src[0]);
     const src_scalars s1 = make_scalars(one ? P.src[0] : P.src[1]);
     const bool do_stats = P.stats != nullptr;
 
-    // XCD-aware tile assignment, waves as the unit (as wgrad_wp.h): blocks b and b + 8 share an XCD, which owns a contiguous eighth of the tiles;
-    // its waves take them round-robin, so the tiles in flight on an XCD are neighbours (halo rows hit in its L2)
-    const int nb = gridDim.x;
-    const int NG = nb < 8 ? nb : 8;
-    const int xcd = blockIdx.x % NG;
-    const int sj = ((int)blockIdx.x / NG) * 4 + wave;
-    const int bpx = ((nb + NG - 1 - xcd) / NG) * 4;
-    const long per = (ntiles + NG - 1) / NG;
-    const long t_lo = per * xcd, t_hi = t_lo + per < ntiles ? t_lo + per : ntiles;
-    const long my_tiles = (bpx > 0 && t_lo + sj < t_hi) ? (t_hi - t_lo - sj + bpx - 1) / bpx : 0;
-    const long last_tile = t_lo + sj + (my_tiles > 0 ? my_tiles - 1 : 0) * bpx;
-    auto tile_of = [&](long k) __attribute__((always_inline)) { const long t = t_lo + sj + k * bpx; return t < last_tile ? t : last_tile; };
+    const wp_tile_walk walk((int)gridDim.x, (int)blockIdx.x, wave, ntiles);
+    const long my_tiles = walk.my_tiles;
 
     unit_desc<UNITS> U;
     make_units_wave<G, GPT, PS, UNITS>(U, P.IH, P.IW, lane);
@@ -79,7 +68,7 @@ __device__ __forceinline__ void conv_wp_kernel(const chap_conv_params& P) {
         halo_issue_impl<T, G, false, 1, KC, false, UNITS, LANESEL, false>(R, U, s0, s1, 1, P.IH, P.IW, nn, 0, ny0, nx0, 0);
     };
     // ---- prologue: every global load first (first halo, scale / shift, weights, bias), then the dependent LDS stores
-    if (my_tiles > 0) issue(tile_of(0));
+    if (my_tiles > 0) issue(walk.tile_of(0));
     float asc[2], ash[2];                                       // thread t < 64: source t / 32, channel t % 32
     {
         const int s_ = threadIdx.x >> 5, c = threadIdx.x & 31;
@@ -124,7 +113,7 @@ __device__ __forceinline__ void conv_wp_kernel(const chap_conv_params& P) {
             frag<T>::store(wlds + (size_t)i * 8, (nt0 + (int)t < ntiles_total) ? wreg[k] : frag<T>::zero());
         }
     }
-    int xoff[STEPS];                                            // LDS element offset of this lane's pixel fragment (row 0), -1 = zero fragment
+    int xoff[STEPS];                                            // LDS element offset of this lane's pixel fragment (row 0), -1 = zero fragment (load_xfrag)
 #pragma unroll
     for (int step = 0; step < STEPS; ++step) {
         const int p = step * 4 + g;
@@ -134,17 +123,15 @@ __device__ __forceinline__ void conv_wp_kernel(const chap_conv_params& P) {
     }
     int ooff[NT];
 #pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        const int nl = (nt0 + t) * 16 + 4 * g;
-        ooff[t] = px * P.out_ld + P.out_coff + ((P.out2 && nl >= P.out2_from) ? nl - P.out2_from : nl);
-    }
+    for (int t = 0; t < NT; ++t) ooff[t] = cl_out_offset(P, (nt0 + t) * 16 + 4 * g, px);
     const int orow = P.W * P.out_ld;
     __syncthreads();                                            // weights and the scale / shift cache are visible: the only block barrier before the end
     if (my_tiles > 0) {
         halo_commit_impl<T, KC, false, UNITS, LANESEL, true, false, CWP_AFFC>(R, U, halo, s0, s1, aff, plain, nn, 0);
+        wp_lds_committed();
         for (long k = 0;; ++k) {
             n = nn; y0 = ny0; x0 = nx0;
-            issue(tile_of(k + 1));                              // (the tail re-requests the wave's last tile: every prefetch register is consumed on every path)
+            issue(walk.tile_of(k + 1));
             // ---- MFMA over the taps: pixel fragments of the 4 rows from this wave's halo, weight fragments from the block's LDS copy
             f32x4 acc[ROWS][NT];
 #pragma unroll
@@ -156,12 +143,8 @@ __device__ __forceinline__ void conv_wp_kernel(const chap_conv_params& P) {
                 F wf[NT], xf[ROWS];
 #pragma unroll
                 for (int t = 0; t < NT; ++t) wf[t] = frag<T>::load(wlds + ((size_t)(step * NT + t) * 64 + lane) * 8);
-                const int xo = xoff[step];
 #pragma unroll
-                for (int m = 0; m < ROWS; ++m) {
-                    if (step * 4 + 3 < NP) xf[m] = frag<T>::load(halo + xo + m * (G::HW * PS));
-                    else xf[m] = xo >= 0 ? frag<T>::load(halo + xo + m * (G::HW * PS)) : frag<T>::zero();
-                }
+                for (int m = 0; m < ROWS; ++m) xf[m] = load_xfrag<T, NP>(halo, xoff[step], m * (G::HW * PS), step);
 #pragma unroll
                 for (int m = 0; m < ROWS; ++m)
 #pragma unroll
@@ -194,11 +177,13 @@ __device__ __forceinline__ void conv_wp_kernel(const chap_conv_params& P) {
                 }
             }
             if (k + 1 >= my_tiles) break;                       // (leave BEFORE the commit: see conv_fwd_kernel)
+            wp_lds_consumed();
             halo_commit_impl<T, KC, false, UNITS, LANESEL, true, false, CWP_AFFC>(R, U, halo, s0, s1, aff, plain, nn, 0);
+            wp_lds_committed();
         }
     }
-    // ---- BatchNorm statistics: registers -> 16-lane DPP reduce -> LDS row of this wave -> the four rows in a fixed order -> this block's partial slot
     if (do_stats) {
+        // (the wave's row, conv_stats_row's layout, written in place: through the function the register allocation of some instances moves)
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
 #pragma unroll
@@ -210,14 +195,6 @@ __device__ __forceinline__ void conv_wp_kernel(const chap_conv_params& P) {
                 }
             }
         }
-        __syncthreads();
-        if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *(int*)P.stats = (int)gridDim.x;      // header: slots in use
-        float* st = P.stats + CHAP_STATS_HDR + (long)blockIdx.x * 2 * P.Cout;
-        for (int i = threadIdx.x; i < 2 * 16 * NT; i += 256) {
-            const int which = i / (16 * NT), kk = i % (16 * NT);
-            const int nl = nt0 * 16 + kk;
-            const float v = (bstat[(0 * 2 + which) * 16 * NT + kk] + bstat[(1 * 2 + which) * 16 * NT + kk]) + (bstat[(2 * 2 + which) * 16 * NT + kk] + bstat[(3 * 2 + which) * 16 * NT + kk]);
-            if (nl < P.Cout) st[which * P.Cout + nl] = v;
-        }
+        conv_stats_flush<NT>(bstat, P.stats, P.Cout, nt0);
     }
 }

@@ -64,7 +64,7 @@ __device__ __forceinline__ void conv_c1_fwd_kernel(const chap_conv_c1_params& P)
 #pragma unroll
         for (int c = 0; c < CO; c += 8) st8(o + c, acc + c);
     }
-    if (P.stats) {          // this block's partial slot: fixed-order wave butterfly, the four waves summed in a fixed order
+    if (P.stats) {          // this block's partial slot, the format of conv_stats_flush (conv_parts.h): CO channels per thread, so a fixed-order wave butterfly, then the four waves in the same fixed order
 #pragma unroll
         for (int c = 0; c < CO; ++c) {
             const float s = wave_sum(ssum[c]), q = wave_sum(ssq[c]);

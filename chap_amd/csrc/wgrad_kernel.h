@@ -103,9 +103,8 @@ __device__ __forceinline__ void wgrad_kernel(const wgrad_args& A, int nb) {     
     const src_scalars s0 = make_scalars(P.a[0]);
     const src_scalars s1 = make_scalars(P.na > 1 ? P.a[1] : P.a[0]);
     const src_scalars sb = make_scalars(P.b);
-    const bool plainA = !ADD2 && P.a[0].scale == nullptr && !P.a[0].act && P.a[0].keep == nullptr && P.a[0].chan_mul == nullptr &&
-                        (P.na < 2 || (P.a[1].scale == nullptr && !P.a[1].act && P.a[1].keep == nullptr && P.a[1].chan_mul == nullptr));
-    const bool plainB = P.b.scale == nullptr && !P.b.act && P.b.keep == nullptr && P.b.chan_mul == nullptr;
+    const bool plainA = !ADD2 && src_is_plain(P.a[0]) && (P.na < 2 || src_is_plain(P.a[1]));
+    const bool plainB = src_is_plain(P.b);
 
     // ---- one-time per thread: unit descriptors
     unit_desc<UNITS> U;
@@ -129,14 +128,8 @@ __device__ __forceinline__ void wgrad_kernel(const wgrad_args& A, int nb) {     
     }
     // affine caches
 #pragma unroll
-    for (int s = 0; s < 3; ++s) {                                 // (unrolled: a runtime index into the argument block puts its pointers in scratch)
-        const chap_src_t& src = s == 2 ? P.b : P.a[s < P.na ? s : 0];
-        const bool has = src.scale != nullptr;
-        for (int c = threadIdx.x; c < src.C && c < AFFC / 2; c += 256) {
-            aff[s * AFFC + c] = has ? src.scale[c] : 1.f;
-            aff[s * AFFC + AFFC / 2 + c] = has ? src.shift[c] : 0.f;
-        }
-    }
+    for (int s = 0; s < 3; ++s)                                   // (unrolled: a runtime index into the argument block puts its pointers in scratch)
+        aff_cache_fill<AFFC>(aff + s * AFFC, s == 2 ? P.b : P.a[s < P.na ? s : 0]);
 
     f32x4 acc[MAXP][NTB];
 #pragma unroll

@@ -71,22 +71,14 @@ __device__ __forceinline__ void wgrad_wp_kernel(const wgrad_args& A, int nb) {
     const int split = blockIdx.x, chunk = blockIdx.y;
     const int tiles_x = (P.W + G::TW - 1) / G::TW, tiles_y = (P.H + G::TH - 1) / G::TH;
     const long ntiles = (long)P.N * tiles_y * tiles_x;
-    // XCD-aware tile assignment as in wgrad_kernel, one level finer: the "splits" are waves.  Blocks s and s + 8 share an XCD; the XCD owns a
-    // contiguous eighth of the tiles and its waves take them round-robin (the tiles in flight on an XCD are neighbours: halo rows hit in its L2).
-    const int NG = nsplit < 8 ? nsplit : 8;
-    const int xcd = split % NG;
-    const int sj = (split / NG) * 4 + wave;
-    const int bpx = ((nsplit + NG - 1 - xcd) / NG) * 4;
-    const long per = (ntiles + NG - 1) / NG;
-    const long t_lo = per * xcd, t_hi = t_lo + per < ntiles ? t_lo + per : ntiles;
-    const long my_tiles = (bpx > 0 && t_lo + sj < t_hi) ? (t_hi - t_lo - sj + bpx - 1) / bpx : 0;
+    const wp_tile_walk walk(nsplit, split, wave, ntiles);       // (as in wgrad_kernel, one level finer: the "splits" are waves)
+    const long my_tiles = walk.my_tiles;
 
     const src_scalars s0 = make_scalars(P.a[0]);
     const src_scalars s1 = make_scalars(P.na > 1 ? P.a[1] : P.a[0]);
     const src_scalars sb = make_scalars(P.b);
-    const bool plainA = P.a[0].scale == nullptr && !P.a[0].act && P.a[0].keep == nullptr && P.a[0].chan_mul == nullptr &&
-                        (P.na < 2 || (P.a[1].scale == nullptr && !P.a[1].act && P.a[1].keep == nullptr && P.a[1].chan_mul == nullptr));
-    const bool plainB = P.b.scale == nullptr && !P.b.act && P.b.keep == nullptr && P.b.chan_mul == nullptr;
+    const bool plainA = src_is_plain(P.a[0]) && (P.na < 2 || src_is_plain(P.a[1]));
+    const bool plainB = src_is_plain(P.b);
 
     unit_desc<UNITS> U;
     make_units_wave<G, GPT, PS, UNITS>(U, P.IH, P.IW, lane);
@@ -107,14 +99,7 @@ __device__ __forceinline__ void wgrad_wp_kernel(const wgrad_args& A, int nb) {
             b_lds[j] = pix * PSB + bc8;
         }
     }
-    for (int s = 0; s < 3; ++s) {
-        const chap_src_t& src = s == 2 ? P.b : P.a[s < P.na ? s : 0];
-        const bool has = src.scale != nullptr;
-        for (int c = threadIdx.x; c < src.C && c < WP_AFFC / 2; c += 256) {
-            aff[s * WP_AFFC + c] = has ? src.scale[c] : 1.f;
-            aff[s * WP_AFFC + WP_AFFC / 2 + c] = has ? src.shift[c] : 0.f;
-        }
-    }
+    for (int s = 0; s < 3; ++s) aff_cache_fill<WP_AFFC>(aff + s * WP_AFFC, s == 2 ? P.b : P.a[s < P.na ? s : 0]);
 
     f32x4 acc[PAIRS][NTB];
 #pragma unroll
@@ -198,16 +183,14 @@ __device__ __forceinline__ void wgrad_wp_kernel(const wgrad_args& A, int nb) {
     const int a_lane = (rowl * G::HW + xb + qq) * PS + 4 * pp;
     const int b_off = (rowl * G::TW + xb + qq) * PSB + 4 * pp;
 
-    const long last_tile = t_lo + sj + (my_tiles > 0 ? my_tiles - 1 : 0) * bpx;
-    auto tile_of = [&](long k) __attribute__((always_inline)) { const long t = t_lo + sj + k * bpx; return t < last_tile ? t : last_tile; };
-    if (my_tiles > 0) issue(S, tile_of(0));
+    if (my_tiles > 0) issue(S, walk.tile_of(0));
     __syncthreads();                                            // affine caches visible (the only block barrier before the end)
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         ba[k] = *(const f32x2*)(aff + 2 * WP_AFFC + cbB_safe + 2 * k);
         bb2[k] = *(const f32x2*)(aff + 2 * WP_AFFC + WP_AFFC / 2 + cbB_safe + 2 * k);
     }
-    if (my_tiles > 0) commit(S);
+    if (my_tiles > 0) { commit(S); wp_lds_committed(); }
 
     auto compute = [&]() __attribute__((always_inline)) {
         constexpr int NSTEP = NKCH * PAIRS, DEPTH = NSTEP < WG_DEPTH ? NSTEP : WG_DEPTH;
@@ -244,10 +227,12 @@ __device__ __forceinline__ void wgrad_wp_kernel(const wgrad_args& A, int nb) {
     // tile k is in this wave's LDS region: request tile k + 1 (registers), compute tile k, then land tile k + 1 over it
     if (my_tiles > 0) {
         for (long k = 0;; ++k) {
-            issue(S, tile_of(k + 1));
+            issue(S, walk.tile_of(k + 1));
             compute();
             if (k + 1 >= my_tiles) break;                       // (leave BEFORE the commit: see conv_fwd_kernel)
+            wp_lds_consumed();
             commit(S);
+            wp_lds_committed();
         }
     }
     // ---- the four pipelines meet: dW registers -> LDS (each wave into its own tile region) -> summed in a fixed order -> the block's slab
