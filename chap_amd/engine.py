@@ -326,7 +326,8 @@ class Executor:
                 max_total = max(max_total, int(e.total))
         arr = (L.PackEntry * len(entries))(*entries)
         host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
-        return dict(bufs=bufs, table=host.to(dev), n=len(entries), max_total=max_total, key=sd[self.prog.ops[0].w].data_ptr())
+        # (`entries`: the host-side copy of the table, for whoever has to know what the launch touches -- tests/issue_trace.py)
+        return dict(bufs=bufs, table=host.to(dev), entries=arr, n=len(entries), max_total=max_total, key=sd[self.prog.ops[0].w].data_ptr())
 
     def _ensure_packed(self, dtype, sd):
         tab = self._packed.get(dtype)

@@ -20,10 +20,16 @@ bit-identity tests of tests/test_parallel_gpu.py.
 `python -m tests.issue_trace DIR [case ...]` writes every case's full record to DIR/<case>.txt and the fixture lines (case name,
 SHA-256 of the record, counts) to DIR/summary.txt; tests/golden/issue_order_parent.txt is such a summary, made on the commit BEFORE the
 executor's and the training step's schedules were rewritten (tests/test_issue_order_gpu.py).
+
+RichRecorder keeps a second record beside that one, which `text()` and its hashes do not see: every launch with the memory it reads and
+writes, torch's own device work, the host's waits (`python -m tests.issue_trace --rich DIR [case ...]` writes DIR/<case>.rich.txt).
+tests/launch_order.py checks on it that every two launches which meet in memory are ordered (tests/test_launch_order_gpu.py).
 """
+import bisect
 import contextlib
 import hashlib
 import os
+import re
 import sys
 
 import torch
@@ -36,6 +42,10 @@ class Recorder:
         self.lines, self.only_capturing = [], only_capturing
         self._streams, self._events, self._keep = {}, {}, []
         self._region, self._lane, self._nregions = None, 0, 0
+
+    def _line(self, line):
+        """One line of the record (RichRecorder keeps a second record beside it)."""
+        self.lines.append(line)
 
     def _on(self):
         return not self.only_capturing or torch.cuda.is_current_stream_capturing()
@@ -53,7 +63,7 @@ class Recorder:
     def launch(self, name, stream):
         if self._on():
             where = "" if self._region is None else " g%d l%d" % (self._region, self._lane)
-            self.lines.append("L %s %s%s" % (name, self._s(stream), where))
+            self._line("L %s %s%s" % (name, self._s(stream), where))
 
     @contextlib.contextmanager
     def recording(self):
@@ -74,35 +84,35 @@ class Recorder:
         def r_enter(self):
             if self.enabled and rec._on():
                 rec._region, rec._lane, rec._nregions = rec._nregions, 0, rec._nregions + 1
-                rec.lines.append("GB %s g%d" % (rec._s(self.stream), rec._region))
+                rec._line("GB %s g%d" % (rec._s(self.stream), rec._region))
             return g_enter(self)
 
         def r_next(self):
             if self.enabled and rec._region is not None:
                 rec._lane += 1
-                rec.lines.append("GN g%d l%d" % (rec._region, rec._lane))
+                rec._line("GN g%d l%d" % (rec._region, rec._lane))
             return g_next(self)
 
         def r_exit(self, et, ev, tb):
             if self.enabled and rec._region is not None:
-                rec.lines.append("GE g%d" % rec._region)
+                rec._line("GE g%d" % rec._region)
                 rec._region = None
             return g_exit(self, et, ev, tb)
 
         def r_wait_stream(self, stream):
             if rec._on():
-                rec.lines.append("WS %s %s" % (rec._s(self.cuda_stream), rec._s(stream.cuda_stream)))
+                rec._line("WS %s %s" % (rec._s(self.cuda_stream), rec._s(stream.cuda_stream)))
             return wait_stream(self, stream)
 
         def r_wait_event(self, event):
             if rec._on():
-                rec.lines.append("WE %s %s" % (rec._s(self.cuda_stream), rec._e(event)))
+                rec._line("WE %s %s" % (rec._s(self.cuda_stream), rec._e(event)))
             return wait_event(self, event)
 
         def r_record(self, stream=None):
             if rec._on():
                 st = torch.cuda.current_stream() if stream is None else stream
-                rec.lines.append("ER %s %s" % (rec._e(self), rec._s(st.cuda_stream)))
+                rec._line("ER %s %s" % (rec._e(self), rec._s(st.cuda_stream)))
             return ev_record(self, stream)
 
         try:
@@ -116,6 +126,343 @@ class Recorder:
 
     def text(self):
         return "\n".join(self.lines) + "\n"
+
+
+# ---------------------------------------------------------------------------------------------------------------- the rich record
+class _Allocations:
+    """The caching allocator's live blocks.  The base is torch.cuda.memory_snapshot(); reading it costs more than recording a launch and a
+    step allocates in front of almost every launch, so it is read lazily: the dispatch mode reports every allocation it sees (note(): the
+    storage of a fresh result, address and bytes) into an overlay on top of the last snapshot, and the snapshot is read again only when
+    that cannot be the whole truth -- the allocator's counters (torch.cuda.memory_stats) show more allocations than were reported, a
+    segment came or went, a pointer lies in no known block, or it lies in a snapshot block that a reported allocation has since
+    overlapped.  A block freed and not handed out again stays "live" until the next reading; once it is handed out again the record
+    names the same bytes, which is what the order check works on.  `exact` reads the snapshot whenever any counter has moved, frees
+    included: a pointer into a freed block is then a finding at the launch that carries it (three to five times the recording time;
+    tests/test_launch_order_gpu.py records the four default steps this way).  Segments are labelled A0, A1, ... in order of first appearance; an
+    address is written as label + offset inside its segment, so a reused address keeps its name."""
+
+    def __init__(self, exact=False):
+        self.labels, self.snapshots, self.exact = {}, 0, exact
+        self._starts, self._blocks, self._segments, self._seg_starts, self._counter, self._fresh = [], [], [], [], None, False
+        self._over_starts, self._over, self._seen = [], [], 0
+
+    @staticmethod
+    def _moved():
+        st = torch.cuda.memory_stats_as_nested_dict()          # (not memory_stats(): flattening it costs more than the launch being recorded)
+        return tuple(st[k]["all"][d] for k in ("allocation", "segment") for d in ("allocated", "freed"))
+
+    def _read(self):
+        blocks, segments = [], []
+        for seg in torch.cuda.memory_snapshot():
+            at = seg["address"]
+            segments.append((seg["address"], seg["total_size"]))
+            for b in seg["blocks"]:
+                at = b.get("address", at)
+                if b["state"] == "active_allocated":
+                    blocks.append((at, b["size"], seg["address"]))
+                at += b["size"]
+        blocks.sort()
+        segments.sort()
+        self._blocks, self._starts, self._segments, self._seg_starts = blocks, [b[0] for b in blocks], segments, [g[0] for g in segments]
+        self._over_starts, self._over = [], []
+        self.snapshots += 1
+        self._fresh = True
+
+    @staticmethod
+    def _in(starts, items, ptr):
+        i = bisect.bisect_right(starts, ptr) - 1
+        if i >= 0 and ptr < items[i][0] + items[i][1]:
+            return items[i]
+        return None
+
+    def note(self, ptr, nbytes):
+        """An allocation the dispatch mode has seen: [ptr, ptr + nbytes) is live now, whatever was noted there before is gone."""
+        self._seen += 1
+        lo = bisect.bisect_right(self._over_starts, ptr) - 1
+        if lo < 0 or self._over[lo][0] + self._over[lo][1] <= ptr:
+            lo += 1
+        hi = bisect.bisect_left(self._over_starts, ptr + nbytes)
+        seg = self._in(self._seg_starts, self._segments, ptr)
+        self._over[lo:hi] = [(ptr, nbytes, seg[0] if seg else None)]
+        self._over_starts[lo:hi] = [ptr]
+
+    def sync(self):
+        """Once per recorded launch, in front of its pointers: has the allocator done anything the overlay does not know of?"""
+        now = self._moved()
+        self._fresh = False
+        if now != self._counter:
+            if self.exact or self._counter is None or now[2:] != self._counter[2:] or now[0] - self._counter[0] != self._seen:
+                self._read()
+            self._counter = now
+        self._seen = 0
+
+    def block(self, ptr):
+        """(address, bytes, segment address) of the live allocation around ptr, or None."""
+        for attempt in range(2):
+            blk = self._in(self._over_starts, self._over, ptr)
+            if blk is None:
+                blk = self._in(self._starts, self._blocks, ptr)
+                if blk is not None:          # stale if something has been allocated on top of it since the snapshot
+                    i = bisect.bisect_left(self._over_starts, blk[0] + blk[1])
+                    if i > 0 and self._over[i - 1][0] + self._over[i - 1][1] > blk[0]:
+                        blk = None
+            if blk is not None and blk[2] is not None:
+                return blk
+            if self._fresh:
+                return None
+            self._read()
+        return None
+
+    def label(self, segment):
+        return self.labels.setdefault(segment, "A%d" % len(self.labels))
+
+
+_NO_DEVICE_WORK = ("aten::empty", "aten::new_empty", "aten::_efficientzerotensor")      # allocations: a result, nothing written
+
+
+class RichRecorder(Recorder):
+    """Recorder with a second record beside the first (`rich_text()`; `text()` is unchanged, byte for byte): every L line carries the
+    launch's accesses (tests/launch_access.py: field, mode, extent relative to the live allocation's segment), torch's own device work is
+    there (T lines, through a TorchDispatchMode: reads are the device tensors among the arguments, writes those the op's schema marks
+    as written plus the results that are no views; the extent is the span of the tensor's elements; the stream is the current one), and
+    so are the host's waits (HS torch.cuda.synchronize, SS Stream.synchronize and the device-to-host copies that wait for their stream,
+    ES Event.synchronize) and graph replays (GR, with the accesses in `replay_accesses`: the union of what the capture recorded).  A
+    non-null pointer in no live allocation and an extent that leaves its allocation are findings (X lines).  tests/launch_order.py
+    reads the format.  `pack_entries(device pointer)` returns the host-side PackEntry array behind a chap_pack_multi table."""
+
+    def __init__(self, only_capturing=False, allocations=None, pack_entries=None, replay_accesses=""):
+        super().__init__(only_capturing)
+        self.rich, self._pending = [], ""
+        self.allocs = allocations or _Allocations()
+        self.pack_entries, self.replay_accesses = pack_entries, replay_accesses
+
+    def _line(self, line):
+        self.lines.append(line)
+        self.rich.append(line + self._pending)
+        self._pending = ""
+
+    def _rs(self, handle):
+        """The label of a stream in lines that only the rich record has.  A stream (or event) that the first record has not met yet must not
+        get its label here -- labels go by first appearance in THAT record -- so it is written as a placeholder that rich_text() resolves."""
+        handle = int(handle or 0)
+        return self._streams[handle] if handle in self._streams else "@s%d@" % handle
+
+    def _re(self, event):
+        if id(event) in self._events:
+            return self._events[id(event)]
+        self._keep.append(event)
+        return "@e%d@" % id(event)
+
+    def rich_text(self):
+        text = "\n".join(self.rich) + "\n"
+        streams = dict(("@s%d@" % h, label) for h, label in self._streams.items())
+        events = dict(("@e%d@" % i, label) for i, label in self._events.items())
+        for token in dict.fromkeys(re.findall(r"@[se]\d+@", text)):        # what the first record never met: further labels, by first appearance here
+            table = streams if token[1] == "s" else events
+            if token not in table:
+                table[token] = "%s%d" % (token[1], len(table))
+            text = text.replace(token, table[token])
+        return text
+
+    # ------------------------------------------------------------------------------------------------------------ accesses
+    def _extent(self, what, addr, ext):
+        """The extent text of one access (whole live allocation when the field has no rule), or None: nothing to touch, or an X line written."""
+        from tests.launch_order import format_extent
+        blk = self.allocs.block(addr)
+        if blk is None:
+            self.rich.append("X %s: pointer in no live allocation" % what)
+            return None
+        start, size, segment = blk
+        if ext is None:
+            ext = (start, 0, size, 1)
+        else:
+            lo, hi = ext[0], ext[0] + (ext[3] - 1) * ext[1] + ext[2]
+            if hi <= lo:
+                return None
+            if lo < start or hi > start + size:
+                self.rich.append("X %s: extent [%d, %d) leaves its allocation of %d bytes (pointer at +%d)" % (what, lo - start, hi - start, size, addr - start))
+        return format_extent(self.allocs.label(segment), ext[0] - segment, ext)
+
+    def _access_text(self, name, acc):
+        self.allocs.sync()
+        out = []
+        for path, mode, addr, ext in acc:
+            e = self._extent("%s %s" % (name, path), addr, ext)
+            if e is not None:
+                out.append("%s:%s:%s" % (path, mode, e))
+        return " | " + " ".join(out)
+
+    @staticmethod
+    def _span(t):
+        """The bytes between a tensor's first and last element (an upper bound of a strided view, exact for a contiguous one)."""
+        if t.numel() == 0:
+            return None
+        last = sum((n - 1) * abs(s) for n, s in zip(t.shape, t.stride()))
+        return (t.data_ptr(), 0, (last + 1) * t.element_size(), 1)
+
+    @staticmethod
+    def _is_dev(t):
+        return t.is_cuda
+
+    def _cur(self):
+        return self._rs(torch.cuda.current_stream().cuda_stream)
+
+    def note_results(self, args, kwargs, result):
+        """Tell the allocation map about every fresh device storage among an op's results (recording or not: the map has to stay true)."""
+        def tensors(value):
+            if isinstance(value, torch.Tensor):
+                if self._is_dev(value):
+                    yield value
+            elif isinstance(value, (list, tuple)):
+                for v in value:
+                    yield from tensors(v)
+        fresh = [t for t in tensors(result)]
+        if not fresh:
+            return
+        known = {t.untyped_storage().data_ptr() for t in tensors(args)} | {t.untyped_storage().data_ptr() for t in tensors(tuple(kwargs.values()))}
+        for t in fresh:
+            st = t.untyped_storage()
+            if st.data_ptr() and st.data_ptr() not in known and st.nbytes():
+                known.add(st.data_ptr())
+                self.allocs.note(st.data_ptr(), st.nbytes())
+
+    def torch_op(self, func, args, kwargs, result):
+        if not self._on():
+            return
+        schema = func._schema
+        if schema.name.startswith(_NO_DEVICE_WORK):
+            return
+        reads, writes, storages, host_side = [], [], set(), False
+
+        def visit(value, written, tag):
+            nonlocal host_side
+            if isinstance(value, torch.Tensor):
+                if self._is_dev(value):
+                    storages.add(value.untyped_storage().data_ptr())
+                    (writes if written else reads).append((tag, value))
+                elif written:
+                    host_side = True
+            elif isinstance(value, (list, tuple)):
+                for v in value:
+                    visit(v, written, tag)
+
+        formal = schema.arguments
+        for i, value in enumerate(args):
+            visit(value, bool(formal[i].alias_info and formal[i].alias_info.is_write), "a%d" % i)
+        for i, a in enumerate(formal):
+            if a.name in kwargs:
+                visit(kwargs[a.name], bool(a.alias_info and a.alias_info.is_write), "a%d" % i)
+        seen = set(storages)
+        results = result if isinstance(result, (list, tuple)) else (result,)
+        for i, value in enumerate(results):
+            if isinstance(value, torch.Tensor):
+                if not self._is_dev(value):
+                    host_side = True            # a device-to-host copy (_to_copy, _local_scalar_dense gives a number: below)
+                elif value.untyped_storage().data_ptr() not in seen and not any(value is w for _, w in writes):
+                    writes.append(("out%d" % i, value))         # a fresh result; a view of an argument is no device work
+        if schema.name == "aten::_local_scalar_dense":
+            host_side = True
+        if not writes and not (host_side and reads):
+            return
+        acc = [(tag, "R", t.data_ptr(), self._span(t)) for tag, t in reads] + [(tag, "W", t.data_ptr(), self._span(t)) for tag, t in writes]
+        name = schema.name.split("::")[-1] + ("." + schema.overload_name if schema.overload_name else "")
+        stream = self._cur()
+        self.rich.append("T %s %s%s" % (name, stream, self._access_text(name, [a for a in acc if a[3] is not None])))
+        if host_side and reads and not kwargs.get("non_blocking", False) and not (len(args) > 2 and args[2] is True and schema.name == "aten::copy_"):
+            self.rich.append("SS %s" % stream)          # the host waits for the copy, i.e. for everything its stream was handed before
+
+    # ------------------------------------------------------------------------------------------------------------ patches
+    @contextlib.contextmanager
+    def recording(self):
+        from torch.utils._python_dispatch import TorchDispatchMode
+        from chap_amd import _lib as L
+        from tests import launch_access
+        rec = self
+
+        class Mode(TorchDispatchMode):
+            def __torch_dispatch__(self, func, types, args=(), kwargs=None):
+                kwargs = kwargs or {}
+                out = func(*args, **kwargs)
+                rec.note_results(args, kwargs, out)
+                rec.torch_op(func, args, kwargs, out)
+                return out
+
+        with super().recording():
+            saved = (L.call, L.pack_multi, torch.cuda.synchronize, torch.cuda.Stream.synchronize, torch.cuda.Event.synchronize,
+                     torch.cuda.CUDAGraph.replay)
+            call, pack_multi, dev_sync, stream_sync, event_sync, replay = saved
+
+            def r_call(name, params, stream):
+                if rec._on():
+                    rec._pending = rec._access_text(name, launch_access.accesses(name, params))
+                return call(name, params, stream)
+
+            def r_pack_multi(entries, n, max_total, stream):
+                if rec._on():
+                    host = rec.pack_entries(entries) if rec.pack_entries is not None else None
+                    acc = [("entries", "R", int(entries), None)] + (launch_access.pack_multi_accesses(host[:n]) if host is not None else [])
+                    if host is None:
+                        rec.rich.append("X chap_pack_multi: no host-side entry list for the table at its pointer")
+                    rec._pending = rec._access_text("chap_pack_multi", acc)
+                return pack_multi(entries, n, max_total, stream)
+
+            def r_dev_sync(device=None):
+                out = dev_sync(device)
+                if rec._on():
+                    rec.rich.append("HS")
+                return out
+
+            def r_stream_sync(self):
+                out = stream_sync(self)
+                if rec._on():
+                    rec.rich.append("SS %s" % rec._rs(self.cuda_stream))
+                return out
+
+            def r_event_sync(self):
+                out = event_sync(self)
+                if rec._on():
+                    rec.rich.append("ES %s" % rec._re(self))
+                return out
+
+            def r_replay(self):
+                if rec._on():
+                    rec.rich.append("GR %s | %s" % (rec._cur(), rec.replay_accesses))
+                return replay(self)
+
+            try:
+                L.call, L.pack_multi = r_call, r_pack_multi
+                torch.cuda.synchronize, torch.cuda.Stream.synchronize, torch.cuda.Event.synchronize = r_dev_sync, r_stream_sync, r_event_sync
+                torch.cuda.CUDAGraph.replay = r_replay
+                with Mode():
+                    yield self
+            finally:
+                (L.call, L.pack_multi, torch.cuda.synchronize, torch.cuda.Stream.synchronize, torch.cuda.Event.synchronize,
+                 torch.cuda.CUDAGraph.replay) = saved
+
+
+def union_accesses(rich_text):
+    """The accesses of all L and T lines of a rich record as one access list for a GR line: per allocation label the merged ranges read
+    and the merged ranges written (a row set counts with the range from its first to its last byte: an upper bound)."""
+    from tests.launch_order import parse_extent
+    spans = {}
+    for ln in rich_text.splitlines():
+        head, _, acc = ln.partition(" | ")
+        if head.startswith(("L ", "T ")):
+            for item in acc.split():
+                _, mode, ext = item.split(":", 2)
+                label, (base, pitch, row_bytes, nrows) = parse_extent(ext)
+                spans.setdefault((label, "R" if mode == "R" else "W"), []).append((base, base + (nrows - 1) * pitch + row_bytes))
+    out = []
+    for (label, mode), ranges in sorted(spans.items()):
+        ranges.sort()
+        merged = [list(ranges[0])]
+        for lo, hi in ranges[1:]:
+            if lo <= merged[-1][1]:
+                merged[-1][1] = max(merged[-1][1], hi)
+            else:
+                merged.append([lo, hi])
+        out += ["%s%d:%s:%s+%d:%d" % (mode.lower(), len(out) + i, mode, label, lo, hi - lo) for i, (lo, hi) in enumerate(merged)]
+    return " ".join(out)
 
 
 def counts(text):
@@ -214,8 +561,18 @@ def _environ(env):
                 os.environ[k] = v
 
 
-def record_case(name):
-    """Run one case on the GPU and return its full text record."""
+def _pack_entries_of(model):
+    """device pointer of a chap_pack_multi table -> the host-side PackEntry array the executor built it from"""
+    def find(ptr):
+        for tab in model._exec._packed.values():
+            if tab["table"].data_ptr() == int(ptr):
+                return tab["entries"]
+        return None
+    return find
+
+
+def _case_step(name):
+    """(step, inputs, injected randomness, environment) of one case: the model with the case's state, its training step not yet run."""
     from chap_amd.networks import DualDecoder, DualDecoder3d
     from chap_amd.train import AblationStep, ChapStep
     case = CASES[name]
@@ -235,15 +592,46 @@ def record_case(name):
         inj.update(fp_uniforms=[(a.to(DEV), b.to(DEV)) for a, b in uniforms], sim_score=[sc.to(DEV) for sc in scores])
     with _environ(case.get("env", {})):
         step = (AblationStep if case.get("step") == "ablation" else ChapStep)(m, dict(inp["args"], **case.get("args", {})))
-        step.iter_num = 4500
-        rec = Recorder(only_capturing=case["mode"] == "captured")
+    step.iter_num = 4500
+    return step, inp, inj
+
+
+def record_case(name, rich=False, exact=False):
+    """Run one case on the GPU and return its full text record; with `rich`, (that record, the rich record) of a RichRecorder (`exact`:
+    with the allocator's snapshot read after every allocation and free, _Allocations)."""
+    case = CASES[name]
+    step, inp, inj = _case_step(name)
+    with _environ(case.get("env", {})):
+        only = case["mode"] == "captured"
+        rec = RichRecorder(only, _Allocations(exact), pack_entries=_pack_entries_of(step.model)) if rich else Recorder(only)
         with rec.recording():
             if case["mode"] == "eager":
                 step.step(inp["vol"], inp["lab"], box_yx=inp["box"], inject=inj)
             else:
                 step.capture(inp["vol"], inp["lab"], warmup=1, inject=inj)
         torch.cuda.synchronize()
-    return rec.text()
+    return (rec.text(), rec.rich_text()) if rich else rec.text()
+
+
+STAGED_REPLAY = "2d_staged_double_replay"       # not in CASES: it has no record of the first kind in tests/golden/issue_order_parent.txt
+
+
+def record_staged_replays():
+    """The rich record of two consecutive replay() calls of the captured 2D step that take their batch from stage() (ChapStep._stage: the
+    copy stream and its two events).  A replay is one GR line on its stream whose accesses are the union of what the capture recorded;
+    the copies into the staging and the static buffers come from the dispatch mode.  Returns (record of the capture, record of the replays)."""
+    step, inp, inj = _case_step("2d_captured")
+    cap = RichRecorder(True, pack_entries=_pack_entries_of(step.model))
+    with cap.recording():
+        step.capture(inp["vol"], inp["lab"], warmup=1, inject=inj)
+    torch.cuda.synchronize()
+    rec = RichRecorder(False, allocations=cap.allocs, pack_entries=cap.pack_entries, replay_accesses=union_accesses(cap.rich_text()))
+    with rec.recording():
+        for _ in range(2):
+            step.stage(inp["vol"], inp["lab"])
+            step.replay(box_yx=inp["box"])
+    torch.cuda.synchronize()
+    return cap.rich_text(), rec.rich_text()
 
 
 def write_records(directory, names=None):
@@ -261,5 +649,32 @@ def write_records(directory, names=None):
     return out
 
 
+def write_rich_records(directory, names=None):
+    """Every case's rich record to `directory`/<case>.rich.txt, the staged double replay (STAGED_REPLAY) included when asked for by name
+    or when no names are given; tests/golden/launch_order_2d_captured.txt.gz is such a file (2d_captured), gzipped.  `directory`/times.txt
+    gets every case's wall time recorded the first way and the rich way, in that order, after one untimed step of each network
+    (profiles/launch_order_times.txt)."""
+    import time
+    os.makedirs(directory, exist_ok=True)
+    record_case("2d_eager"), record_case("3d_eager")
+    times = []
+    for name in names or list(CASES) + [STAGED_REPLAY]:
+        t0 = time.time()
+        if name != STAGED_REPLAY:
+            record_case(name)
+        t1 = time.time()
+        rich = record_staged_replays()[1] if name == STAGED_REPLAY else record_case(name, rich=True)[1]
+        t2 = time.time()
+        with open(os.path.join(directory, name + ".rich.txt"), "w") as f:
+            f.write(rich)
+        times.append("%-28s first record %.2f s   rich record %.2f s   %d lines" % (name, t1 - t0, t2 - t1, len(rich.splitlines())))
+        print(times[-1], flush=True)
+    with open(os.path.join(directory, "times.txt"), "w") as f:
+        f.write("\n".join(times) + "\n")
+
+
 if __name__ == "__main__":
-    write_records(sys.argv[1], sys.argv[2:] or None)
+    if sys.argv[1] == "--rich":
+        write_rich_records(sys.argv[2], sys.argv[3:] or None)
+    else:
+        write_records(sys.argv[1], sys.argv[2:] or None)
