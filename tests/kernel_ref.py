@@ -208,10 +208,14 @@ def stats_ref(r, c=None):
 
 
 # ---- weight gradient --------------------------------------------------------------------------------------------------------------
-def wgrad_ref(A, B, *, ksize, stride, flipA=None, flipB=None):
+def wgrad_ref(A, B, *, ksize, stride, flipA=None, flipB=None, Bv=None, dBv=None):
     """chap_wgrad in fp64: dW[t, kc, kn] = sum_p A[n, kc, p*stride + t - pad] * B[n, kn, p] over the grid of B (pad 1 for k3, else 0).
     A = the conv input's MFMA operand at input resolution, B = the output gradient (a transposed conv passes its fine gradient as A
-    and its coarse lazy input as B; flipB: that operand's boundary term).  Returns dict(dw [taps, Ca, Cb], sabs, fterm, db, db_sabs, chain = pixels of the grid)."""
+    and its coarse lazy input as B; flipB: that operand's boundary term).  Returns dict(dw [taps, Ca, Cb], sabs, fterm, db, db_sabs, db_flip, chain = pixels of the grid).
+    Bv, dBv: the fp32 value of a LAZY B and its uncertainty (lazy_f32's pair), for the bias gradient.  The kernel (wgrad_kernel.h, the commit of a
+    B tile) sums db from the transformed fp32 value v and packs v to the operand type afterwards; a plain B is summed as stored.  So db of a lazy B is
+    sum v, not the sum of the operands: in bf16 the two differ by up to U_BF16 |v| per pixel (independent roundings: about U_BF16 |v| sqrt(pixels) / 3 in
+    all, far above the fp32 chain's gamma(pixels) sum |v|), and in either type the kernel's v may be dBv off the restated one.  Without Bv, db = sum B."""
     dims = A.dim() - 2
     pad = [1 if ksize == 3 else 0] * (2 * dims)
     Ap = F.pad(A, pad)
@@ -227,8 +231,9 @@ def wgrad_ref(A, B, *, ksize, stride, flipA=None, flipB=None):
         if flipB is not None:
             fterm[-1] = fterm[-1] + torch.einsum("nc...,nk...->ck", Ap[win].abs(), flipB)
     red = [0] + list(range(2, B.dim()))
-    return dict(dw=torch.stack(dw), sabs=torch.stack(sabs), fterm=torch.stack(fterm), db=B.sum(red), db_sabs=Bb.sum(red),
-                chain=B[:, 0].numel())
+    Bd = B if Bv is None else Bv
+    return dict(dw=torch.stack(dw), sabs=torch.stack(sabs), fterm=torch.stack(fterm), db=Bd.sum(red), db_sabs=Bd.abs().sum(red),
+                db_flip=dBv.sum(red) if dBv is not None else torch.zeros_like(Bd.sum(red)), chain=B[:, 0].numel())
 
 
 def wgrad_bound(r, prior=None, which="dw"):
@@ -237,7 +242,7 @@ def wgrad_bound(r, prior=None, which="dw"):
     if which == "dw":
         b, tot = bound(r["dw"], sabs=r["sabs"], chain=r["chain"], flip=r["fterm"]), r["dw"]
     else:
-        b, tot = bound(r["db"], sabs=r["db_sabs"], chain=r["chain"]), r["db"]
+        b, tot = bound(r["db"], sabs=r["db_sabs"], chain=r["chain"], flip=r.get("db_flip")), r["db"]
     if prior is not None:
         tot = tot + _c(prior, tot)
     return b + U32 * tot.abs()

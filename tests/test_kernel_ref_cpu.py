@@ -298,6 +298,28 @@ def test_mutation_g_dw_and_db_missing_one_blocks_partial_row():
     assert relerr(got, ref) >= WTOL[dtype] and relerr(db, rw["db"]) >= WTOL[dtype]     # (rejected at this size)
 
 
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_bias_gradient_of_a_lazy_b_is_the_sum_of_its_fp32_values(dtype):
+    """wgrad_ref(Bv=, dBv=): the kernel sums db of a lazy B before the value is packed to the operand type.  An fp32 sum of the fp32 values passes under
+    wgrad_bound(which="db"); in bf16 the sum of the rounded operands does not (and without Bv the reference is that sum, as it was); a plain B has
+    Bv = B and dBv = 0, which changes nothing."""
+    g = torch.Generator().manual_seed(17)
+    x = rq(torch.randn(2, 32, 9, 21, generator=g), dtype)
+    A = rq(torch.randn(2, 16, 18, 42, generator=g), dtype).double()
+    sc_, sh_ = torch.rand(32, generator=g) + 0.5, torch.randn(32, generator=g) * 0.2
+    v, dv = kr.lazy_f32(x, scale=sc_, shift=sh_, act=True, slope=0.01)
+    B, fB = kr.mfma_operand(v, dv, dtype)
+    rw = kr.wgrad_ref(A, B, ksize=2, stride=2, flipB=fB, Bv=v, dBv=dv)
+    old = kr.wgrad_ref(A, B, ksize=2, stride=2, flipB=fB)
+    assert torch.equal(rw["dw"], old["dw"]) and torch.equal(old["db"], B.sum((0, 2, 3))) and torch.equal(rw["db"], v.sum((0, 2, 3)))
+    assert kr.check("db of fp32 values", v.float().sum((0, 2, 3)), rw["db"], kr.wgrad_bound(rw, which="db")) <= 1.0
+    if dtype == torch.bfloat16:
+        assert fails("db of operands", B.float().sum((0, 2, 3)), rw["db"], kr.wgrad_bound(rw, which="db"))
+    plain = kr.wgrad_ref(A, x.double(), ksize=2, stride=2, Bv=x.double(), dBv=torch.zeros_like(x).double())
+    ref = kr.wgrad_ref(A, x.double(), ksize=2, stride=2)
+    assert torch.equal(plain["db"], ref["db"]) and torch.equal(kr.wgrad_bound(plain, which="db"), kr.wgrad_bound(ref, which="db"))
+
+
 # ==== plumbing kernels (losses, VAT / BCP helpers, RNG, diff mask, largest component, SGD) ==========================================
 import numpy as np
 
