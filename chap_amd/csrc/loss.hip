@@ -9,14 +9,22 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+#ifndef CHAP_TOTALS_WIDE
+#define CHAP_TOTALS_WIDE 1      // 0 (timing builds only): rows of more than 32 floats take the column-by-column loop, as before C = 5..8 existed
+#endif
+// Columns per wave of the totals kernel that serves class count C: 8 up to C = 4 (the kernel those counts have always run), 13 from C = 5 on.
+inline int totals_cols_per_wave(int C) { return (C <= 4 || !CHAP_TOTALS_WIDE) ? 8 : 13; }
 // Row 0 of a [1 + nrows][rl] partial workspace <- fixed-order column sums of rows 1..nrows (one wave per column, fp64).
 // Called by all 256 threads of ONE block; `tot` (shared, rl floats) receives the totals too.  Ends with a barrier.
+// NR, a compile-time parameter of the totals kernels: the one-round-trip path below holds rows of up to 4 * NR floats.  NR = 8 is the kernel
+// that C <= 4 has always run (mix_loss rows are 2 (2 + 3C) floats, distance rows 2 (3C + 1): at most 32), NR = 13 covers C = 5..8 (52).
+template <int NR>
 __device__ __forceinline__ void sum_partial_rows(float* ws, int nrows, int rl, float* tot) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (rl <= 32 && nrows <= CHAP_LOSS_SLOTS) {
-        // every load of the block first (a wave's columns wave, wave + 4, ..: at most 8, a lane's rows lane, lane + 64, ..: at most 8),
-        // then the sums in the same fixed order as the loop below -- the kernel is one dependent round trip instead of eight
-        constexpr int NR = 8, NB = CHAP_LOSS_SLOTS / 64;
+    if (rl <= 4 * NR && nrows <= CHAP_LOSS_SLOTS) {
+        // every load of the block first (a wave's columns wave, wave + 4, ..: at most NR, a lane's rows lane, lane + 64, ..: at most 8),
+        // then the sums in the same fixed order as the loop below -- the kernel is one dependent round trip instead of NR
+        constexpr int NB = CHAP_LOSS_SLOTS / 64;
         float v[NR][NB];
 #pragma unroll
         for (int r = 0; r < NR; ++r) {
@@ -112,10 +120,11 @@ template <int C>
 __global__ __launch_bounds__(256) void mix_loss_acc_kernel(const chap_mix_loss_params P_) { mix_loss_acc_body<C>(P_, blockIdx.x, gridDim.x); }
 
 // Totals (row 0 of acc, fixed-order sum of the block partials) and the mix_loss return triple (train_ours_2D.py:205-216).
+template <int NR>
 __device__ __forceinline__ void mix_loss_final_body(float* acc, int nblocks, float* loss, int C, float w_a, float w_b, float smooth, float k_dice, float k_ce) {
     __shared__ float tot[2 * (2 + 3 * 8)];
     const int NA = 2 + 3 * C;
-    sum_partial_rows(acc, nblocks, 2 * NA, tot);
+    sum_partial_rows<NR>(acc, nblocks, 2 * NA, tot);
     if (threadIdx.x != 0) return;
     float part[2];
     const float w[2] = {w_a, w_b};
@@ -129,8 +138,9 @@ __device__ __forceinline__ void mix_loss_final_body(float* acc, int nblocks, flo
     }
     loss[0] = part[0]; loss[1] = part[1]; loss[2] = part[0] + part[1];
 }
+template <int NR>
 __global__ __launch_bounds__(256) void mix_loss_final_kernel(float* acc, int nblocks, float* loss, int C, float w_a, float w_b, float smooth, float k_dice, float k_ce) {
-    mix_loss_final_body(acc, nblocks, loss, C, w_a, w_b, smooth, k_dice, k_ce);
+    mix_loss_final_body<NR>(acc, nblocks, loss, C, w_a, w_b, smooth, k_dice, k_ce);
 }
 
 template <int C>
@@ -184,6 +194,22 @@ constexpr int LOSS_MAX_BLOCKS = 2048;
 __host__ __device__ inline int loss_blocks(long total) { long b = (total + 255) / 256; return (int)(b < LOSS_MAX_BLOCKS ? b : LOSS_MAX_BLOCKS); }
 __host__ __device__ inline int loss_slots(long total) { long b = (total + 255) / 256; return (int)(b < CHAP_LOSS_SLOTS ? b : CHAP_LOSS_SLOTS); }   // kernels that leave one partial row per block
 
+// The class counts the single-term loss kernels are built for, and their one dispatch: KERNEL<C> for the run-time C.  Every instance is
+// the same template; C = 2 and C = 4 are the instances the library has always had.
+constexpr int LOSS_MINC = 2, LOSS_MAXC = 8;
+#define LOSS_LAUNCH(KERNEL, C_, GRID, STREAM, ...)                                                                      \
+    switch (C_) {                                                                                                       \
+        case 2: hipLaunchKernelGGL(KERNEL<2>, dim3(GRID), dim3(256), 0, STREAM, __VA_ARGS__); break;                    \
+        case 3: hipLaunchKernelGGL(KERNEL<3>, dim3(GRID), dim3(256), 0, STREAM, __VA_ARGS__); break;                    \
+        case 4: hipLaunchKernelGGL(KERNEL<4>, dim3(GRID), dim3(256), 0, STREAM, __VA_ARGS__); break;                    \
+        case 5: hipLaunchKernelGGL(KERNEL<5>, dim3(GRID), dim3(256), 0, STREAM, __VA_ARGS__); break;                    \
+        case 6: hipLaunchKernelGGL(KERNEL<6>, dim3(GRID), dim3(256), 0, STREAM, __VA_ARGS__); break;                    \
+        case 7: hipLaunchKernelGGL(KERNEL<7>, dim3(GRID), dim3(256), 0, STREAM, __VA_ARGS__); break;                    \
+        case 8: hipLaunchKernelGGL(KERNEL<8>, dim3(GRID), dim3(256), 0, STREAM, __VA_ARGS__); break;                    \
+        default: break; /* refused by the entry's argument check */                                                     \
+    }
+#define LOSS_CHECK_C(WHO, C_) CHAP_CHECK_ARG((C_) >= LOSS_MINC && (C_) <= LOSS_MAXC, WHO ": C=%d (2..8 built)", C_)
+
 // Up to four independent mix_loss terms in one launch each: grid (max_t nb_t, nterms), blockIdx.y selects the term, and a term's blocks
 // are the first nb_t of its row -- nb_t, the grid-stride step and the partial-row index are those of the single-term launch, so every
 // sum runs in the same order and the results are bit for bit those of nterms single-term calls.
@@ -197,7 +223,7 @@ __global__ __launch_bounds__(256) void mix_loss_multi_acc_kernel(const chap_mix_
 __global__ __launch_bounds__(256) void mix_loss_multi_final_kernel(const chap_mix_loss_multi_params M) {
     const chap_mix_loss_params& P_ = M.term[blockIdx.x];
     const bool dflt = P_.k_dice == 0.f && P_.k_ce == 0.f;
-    mix_loss_final_body(P_.acc, loss_slots((long)P_.N * P_.P), P_.loss, P_.C, P_.w_a, P_.w_b, P_.smooth, dflt ? 0.5f : P_.k_dice, dflt ? 0.5f : P_.k_ce);
+    mix_loss_final_body<8>(P_.acc, loss_slots((long)P_.N * P_.P), P_.loss, P_.C, P_.w_a, P_.w_b, P_.smooth, dflt ? 0.5f : P_.k_dice, dflt ? 0.5f : P_.k_ce);
 }
 template <int C>
 __global__ __launch_bounds__(256) void mix_loss_multi_bwd_kernel(const chap_mix_loss_multi_params M) {
@@ -209,26 +235,26 @@ __global__ __launch_bounds__(256) void mix_loss_multi_bwd_kernel(const chap_mix_
 
 extern "C" int chap_mix_loss_fwd(const chap_mix_loss_params* p, void* stream) {
     CHAP_CHECK_ARG(p && p->logits && p->target_a && p->acc && p->loss, "chap_mix_loss_fwd: null argument");
-    CHAP_CHECK_ARG(p->C == 4 || p->C == 2, "chap_mix_loss: C=%d (2 or 4 built)", p->C);
+    LOSS_CHECK_C("chap_mix_loss", p->C);
     CHAP_CHECK_ARG((long)p->N * p->P < (1L << 32), "chap_mix_loss: N*P=%ld exceeds the 32-bit pixel index", (long)p->N * p->P);
     const int nb = loss_slots((long)p->N * p->P);
     hipStream_t s = (hipStream_t)stream;
-    if (p->C == 4) hipLaunchKernelGGL(mix_loss_acc_kernel<4>, dim3(nb), dim3(256), 0, s, *p);
-    else hipLaunchKernelGGL(mix_loss_acc_kernel<2>, dim3(nb), dim3(256), 0, s, *p);
+    LOSS_LAUNCH(mix_loss_acc_kernel, p->C, nb, s, *p);
     CHAP_LAUNCH_CHECK("chap_mix_loss_fwd");
     const bool dflt = p->k_dice == 0.f && p->k_ce == 0.f;
-    hipLaunchKernelGGL(mix_loss_final_kernel, dim3(1), dim3(256), 0, s, p->acc, nb, p->loss, p->C, p->w_a, p->w_b, p->smooth,
-                       dflt ? 0.5f : p->k_dice, dflt ? 0.5f : p->k_ce);
+    if (totals_cols_per_wave(p->C) == 8)
+        hipLaunchKernelGGL(mix_loss_final_kernel<8>, dim3(1), dim3(256), 0, s, p->acc, nb, p->loss, p->C, p->w_a, p->w_b, p->smooth, dflt ? 0.5f : p->k_dice, dflt ? 0.5f : p->k_ce);
+    else
+        hipLaunchKernelGGL(mix_loss_final_kernel<13>, dim3(1), dim3(256), 0, s, p->acc, nb, p->loss, p->C, p->w_a, p->w_b, p->smooth, dflt ? 0.5f : p->k_dice, dflt ? 0.5f : p->k_ce);
     CHAP_LAUNCH_CHECK("chap_mix_loss_fwd(final)");
     return CHAP_OK;
 }
 extern "C" int chap_mix_loss_bwd(const chap_mix_loss_params* p, void* stream) {
     CHAP_CHECK_ARG(p && p->logits && p->target_a && p->acc && p->dlogits, "chap_mix_loss_bwd: null argument");
-    CHAP_CHECK_ARG(p->C == 4 || p->C == 2, "chap_mix_loss: C=%d (2 or 4 built)", p->C);
+    LOSS_CHECK_C("chap_mix_loss", p->C);
     CHAP_CHECK_ARG((long)p->N * p->P < (1L << 32), "chap_mix_loss: N*P=%ld exceeds the 32-bit pixel index", (long)p->N * p->P);
     const int nb = loss_blocks((long)p->N * p->P);
-    if (p->C == 4) hipLaunchKernelGGL(mix_loss_bwd_kernel<4>, dim3(nb), dim3(256), 0, (hipStream_t)stream, *p);
-    else hipLaunchKernelGGL(mix_loss_bwd_kernel<2>, dim3(nb), dim3(256), 0, (hipStream_t)stream, *p);
+    LOSS_LAUNCH(mix_loss_bwd_kernel, p->C, nb, (hipStream_t)stream, *p);
     CHAP_LAUNCH_CHECK("chap_mix_loss_bwd");
     return CHAP_OK;
 }
@@ -240,7 +266,7 @@ static int mix_loss_multi_check(const chap_mix_loss_multi_params* m, bool bwd, c
     for (int t = 0; t < m->nterms; ++t) {
         const chap_mix_loss_params* p = &m->term[t];
         CHAP_CHECK_ARG(p->logits && p->target_a && p->acc && (bwd ? (const void*)p->dlogits : (const void*)p->loss), "%s: null argument in term %d", who, t);
-        CHAP_CHECK_ARG(p->C == 4 || p->C == 2, "chap_mix_loss: C=%d (2 or 4 built)", p->C);
+        CHAP_CHECK_ARG(p->C == 4 || p->C == 2, "chap_mix_loss: C=%d (2 or 4 built)", p->C);     // the batched launch: the two benchmarked class counts only
         CHAP_CHECK_ARG(p->C == m->term[0].C && p->P == m->term[0].P, "%s: term %d has C=%d P=%d, term 0 C=%d P=%d (C and P are common)", who, t, p->C, p->P,
                        m->term[0].C, m->term[0].P);
         CHAP_CHECK_ARG(p->N > 0 && p->P > 0, "%s: term %d is empty (N=%d P=%d)", who, t, p->N, p->P);
@@ -297,12 +323,11 @@ __global__ __launch_bounds__(256) void pseudo_kernel(const chap_pseudo_params P_
 }
 extern "C" int chap_pseudo_block(const chap_pseudo_params* p, void* stream) {
     CHAP_CHECK_ARG(p && p->logits1 && p->logits2, "chap_pseudo_block: null argument");
-    CHAP_CHECK_ARG(p->C == 4 || p->C == 2, "chap_pseudo_block: C=%d (2 or 4 built)", p->C);
+    LOSS_CHECK_C("chap_pseudo_block", p->C);
     CHAP_CHECK_ARG((p->soft1 == nullptr) == (p->soft2 == nullptr) && (p->arg1 == nullptr) == (p->arg2 == nullptr), "chap_pseudo_block: outputs come in pairs");
     CHAP_CHECK_ARG((long)p->N * p->P < (1L << 32), "chap_pseudo_block: N*P=%ld exceeds the 32-bit pixel index", (long)p->N * p->P);
     const int nb = loss_blocks((long)p->N * p->P);
-    if (p->C == 4) hipLaunchKernelGGL(pseudo_kernel<4>, dim3(nb), dim3(256), 0, (hipStream_t)stream, *p);
-    else hipLaunchKernelGGL(pseudo_kernel<2>, dim3(nb), dim3(256), 0, (hipStream_t)stream, *p);
+    LOSS_LAUNCH(pseudo_kernel, p->C, nb, (hipStream_t)stream, *p);
     CHAP_LAUNCH_CHECK("chap_pseudo_block");
     return CHAP_OK;
 }
@@ -324,7 +349,8 @@ __global__ __launch_bounds__(256) void kl_kernel(const chap_kl_params P_) {
                                          (uintptr_t)P_.dlogits[0] | (uintptr_t)P_.dlogits[1]) & 15) == 0;
     if (quads) {
         // four consecutive pixels per thread: 16-byte loads / stores of every class plane (the kernel sits between the VAT forward and
-        // backward passes, alone on the GPU; one pixel per thread left it at 2 TB/s)
+        // backward passes, alone on the GPU; one pixel per thread left it at 2 TB/s).  Every C = 2..8 takes this path: z, t and g[C][4]
+        // are about 100 live floats at C = 8, which compiles to 95 VGPRs and no scratch (profiles/loss_resource_usage.txt)
         const long totalq = total >> 2;
         for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < totalq; q += (long)gridDim.x * 256) {
             const long i = q << 2;
@@ -419,10 +445,11 @@ __global__ __launch_bounds__(256) void dice_dist_acc_kernel(const chap_kl_params
 constexpr float DICE_DIST_SMOOTH = 1e-10f;
 
 // totals -> row 0; loss += the distance (one thread: deterministic)
+template <int NR>
 __global__ __launch_bounds__(256) void dist_final_kernel(float* ws, int nblocks, int C, int mode, float inv_total, float* loss) {
     __shared__ float tot[2 * (3 * 8 + 1)];
     const int RH = 3 * C + 1;
-    sum_partial_rows(ws, nblocks, 2 * RH, tot);
+    sum_partial_rows<NR>(ws, nblocks, 2 * RH, tot);
     if (threadIdx.x != 0 || !loss) return;
     if (mode == 0) { *loss += tot[0] * inv_total; return; }
     float d = 0.f;
@@ -459,9 +486,14 @@ __global__ __launch_bounds__(256) void dice_dist_grad_kernel(const chap_kl_param
     }
 }
 
+static void dist_final(const chap_kl_params* p, int nb, int mode, long total, hipStream_t s) {
+    if (totals_cols_per_wave(p->C) == 8) hipLaunchKernelGGL(dist_final_kernel<8>, dim3(1), dim3(256), 0, s, p->ws, nb, p->C, mode, 1.f / (float)total, p->loss);
+    else hipLaunchKernelGGL(dist_final_kernel<13>, dim3(1), dim3(256), 0, s, p->ws, nb, p->C, mode, 1.f / (float)total, p->loss);
+}
+
 extern "C" int chap_kl_fwd_bwd(const chap_kl_params* p, void* stream) {
     CHAP_CHECK_ARG(p && p->logits[0] && p->logits[1] && p->target[0] && p->target[1], "chap_kl_fwd_bwd: null argument");
-    CHAP_CHECK_ARG(p->C == 4 || p->C == 2, "chap_kl_fwd_bwd: C=%d (2 or 4 built)", p->C);
+    LOSS_CHECK_C("chap_kl_fwd_bwd", p->C);
     CHAP_CHECK_ARG(p->mode == 0 || p->mode == 1, "chap_kl_fwd_bwd: mode=%d (0 kl, 1 dice)", p->mode);
     CHAP_CHECK_ARG(p->ws || (p->mode == 0 && !p->loss), "chap_kl_fwd_bwd: ws is required for the loss value and for the dice distance");
     const long total = (long)p->N * p->P;
@@ -469,22 +501,19 @@ extern "C" int chap_kl_fwd_bwd(const chap_kl_params* p, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     const int nb = loss_slots(total);
     if (p->mode == 0) {
-        if (p->C == 4) hipLaunchKernelGGL(kl_kernel<4>, dim3(nb), dim3(256), 0, s, *p);
-        else hipLaunchKernelGGL(kl_kernel<2>, dim3(nb), dim3(256), 0, s, *p);
+        LOSS_LAUNCH(kl_kernel, p->C, nb, s, *p);
         CHAP_LAUNCH_CHECK("chap_kl_fwd_bwd");
         if (p->loss) {
-            hipLaunchKernelGGL(dist_final_kernel, dim3(1), dim3(256), 0, s, p->ws, nb, p->C, 0, 1.f / (float)total, p->loss);
+            dist_final(p, nb, 0, total, s);
             CHAP_LAUNCH_CHECK("chap_kl_fwd_bwd(final)");
         }
         return CHAP_OK;
     }
-    if (p->C == 4) hipLaunchKernelGGL(dice_dist_acc_kernel<4>, dim3(nb), dim3(256), 0, s, *p);
-    else hipLaunchKernelGGL(dice_dist_acc_kernel<2>, dim3(nb), dim3(256), 0, s, *p);
-    hipLaunchKernelGGL(dist_final_kernel, dim3(1), dim3(256), 0, s, p->ws, nb, p->C, 1, 1.f / (float)total, p->loss);
+    LOSS_LAUNCH(dice_dist_acc_kernel, p->C, nb, s, *p);
+    dist_final(p, nb, 1, total, s);
     if (p->dlogits[0] || p->dlogits[1]) {
         const int nbg = loss_blocks(total);
-        if (p->C == 4) hipLaunchKernelGGL(dice_dist_grad_kernel<4>, dim3(nbg), dim3(256), 0, s, *p);
-        else hipLaunchKernelGGL(dice_dist_grad_kernel<2>, dim3(nbg), dim3(256), 0, s, *p);
+        LOSS_LAUNCH(dice_dist_grad_kernel, p->C, nbg, s, *p);
     }
     CHAP_LAUNCH_CHECK("chap_kl_fwd_bwd(dice)");
     return CHAP_OK;

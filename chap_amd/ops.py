@@ -338,6 +338,10 @@ def mix_loss_bwd(logits, target_a, target_b, mask, w_a, w_b, acc, dlogits, gscal
     L.call("chap_mix_loss_bwd", p, _stream())
 
 
+LOSS_CLASSES = range(2, 9)              # class counts the loss, pseudo-label and VAT-distance kernels are built for (csrc/loss.hip)
+MIX_LOSS_MULTI_CLASSES = (2, 4)         # ... and the batched multi-term launch: the two benchmarked counts
+
+
 def _fill_mix_loss(p, logits, target_a, target_b, mask, w_a, w_b, acc, smooth, k_dice, k_ce):
     p.logits, p.target_a, p.target_b, p.mask = logits.data_ptr(), target_a.data_ptr(), _p(target_b), _p(mask)
     p.w_a, p.w_b, p.acc = w_a, w_b, acc.data_ptr()

@@ -31,8 +31,9 @@ def synthetic_batch(seed, n_lab, n_unlab, h, w, n_classes=4):
     return imgs, labs
 
 
-def synthetic_batch_3d(seed, n_lab, n_unlab, d, h, w):
-    """Fixed-seed synthetic volumes (LA-like, 2 classes): one anisotropic Gaussian blob = foreground."""
+def synthetic_batch_3d(seed, n_lab, n_unlab, d, h, w, n_classes=2):
+    """Fixed-seed synthetic volumes (LA-like): one anisotropic Gaussian blob = foreground; `n_classes` > 2: nested thresholds of that
+    blob, one region per class, as in synthetic_batch (2 classes: the single threshold 0.5)."""
     g = torch.Generator().manual_seed(seed)
     n = n_lab + n_unlab
     zz, yy, xx = torch.meshgrid(torch.arange(d, dtype=torch.float32), torch.arange(h, dtype=torch.float32),
@@ -51,5 +52,8 @@ def synthetic_batch_3d(seed, n_lab, n_unlab, d, h, w):
             img += 0.5 * torch.rand(1, generator=g) * torch.exp(-(((zz - b[0]) / bs) ** 2 + ((yy - b[1]) / bs) ** 2 + ((xx - b[2]) / bs) ** 2))
         img += 0.05 * torch.randn(d, h, w, generator=g)
         imgs[i, 0] = (img - img.min()) / (img.max() - img.min() + 1e-8)
-        labs[i] = (main > 0.5).long()
+        lab = torch.zeros(d, h, w, dtype=torch.int64)
+        for k in range(1, n_classes):
+            lab[main > (0.25 + 0.5 * k / n_classes)] = k
+        labs[i] = lab
     return imgs, labs

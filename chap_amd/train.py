@@ -99,6 +99,13 @@ FORK_VAT_FORWARD = 4            # the VAT forward passes after the first
 FORK_FINAL_BACKWARD = 8         # the final VAT backward
 
 
+def check_num_classes(nc, who="chap_amd"):
+    """The class counts the training kernels are built for (ops.LOSS_CLASSES: csrc/loss.hip instantiates 2..8; the shared totals arrays, the
+    inference kernels and the V-Net head route end at 8).  The train() entries call this before anything is allocated."""
+    if nc not in ops.LOSS_CLASSES:
+        raise ValueError("%s: num_classes=%r; the training kernels are built for %d to %d classes" % (who, nc, ops.LOSS_CLASSES[0], ops.LOSS_CLASSES[-1]))
+
+
 class VAT2d:
     """adv_loss = VAT2d(xi, epi, num_classes); adv_loss(model, x, soft1, soft2, mask, losstype)
     (call sites train_ours_2D.py:290,372); losstype 'kl' or 'dice' (--adv_losstype, :515), `sign=True` = the FGSM-style
@@ -508,6 +515,9 @@ class ChapStep:
         if split:       # loss_l / loss_u (:352-353) are taken apart: e* holds the unlabeled-supervised parts' gradient
             e1, e2 = torch.empty_like(out_mix1), torch.empty_like(out_mix2)
             eterms = (e1[lsub:], e2[lsub:], e1[:lsub], e2[:lsub])
+        # the batched loss launch is built for the two benchmarked class counts; every other count issues the four single-term calls
+        # below (bit-identical by construction), while largest-CC and the BCP mixing above stay batched: they carry no class limit
+        batch = batch and nc in ops.MIX_LOSS_MULTI_CLASSES
         if batch:       # the four terms are independent: one launch per kernel for all of them (with `split`, the dl set and the e set)
             base = [dict(logits=lg, target_a=img_l, target_b=patch_l, mask=loss_mask) for lg, _, img_l, patch_l, _ in terms]
             wts = [(0.5, 1.0) if unlab else (1.0, 0.5) for *_, unlab in terms]                   # l_weight=1.0, u_weight=0.5 (:198-203)

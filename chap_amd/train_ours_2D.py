@@ -21,7 +21,7 @@ import torch
 from .inference import test_single_volume
 from .networks.net_factory import net_factory
 from .synthetic import synthetic_batch
-from .train import DEFAULT_ARGS, ChapStep
+from .train import DEFAULT_ARGS, ChapStep, check_num_classes
 
 FLAG_DEFAULTS = dict(DEFAULT_ARGS, model="dualdecoder", decoder_type="mcnet", gpu=0, seed=1337, image_size=[256, 256],
                      val_interval=200, labeled_num=7, use_graph=True)          # train_ours_2D.py:469-526
@@ -39,6 +39,7 @@ def _synthetic_loader(a):
 def train(args, snapshot_path):
     a = dict(FLAG_DEFAULTS)
     a.update(args)
+    check_num_classes(a["num_classes"], "chap_amd.train_ours_2D")
     os.makedirs(snapshot_path, exist_ok=True)
     log = logging.getLogger("chap_amd.train")
     log.setLevel(logging.INFO)

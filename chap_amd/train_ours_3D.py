@@ -8,7 +8,8 @@ loader with `next_into`, chap_amd.data.DeviceLoader, feeds the captured iteratio
 `args["labeled_num"]` (the LA h5 layout of test_LA.py:25-28: the first `labeled_num` cases of `train.list` are the labelled ones,
 volumes resident on the device, random crops zero-padded where a volume is smaller than the patch); else the fixed-seed synthetic
 generator.  Validation: `args["val_volumes"]`, a list of (image [w,h,d], label [w,h,d]) arrays, scored by the sliding window of
-chap_amd.test_3d_patch.var_all_case (mean foreground Dice, first decoder).  `dropout=True` is unsupported in 3D (ChapStep raises).
+chap_amd.test_3d_patch.var_all_case (mean foreground Dice, first decoder: binary, whatever `num_classes` (2..8) is -- per-class 3D
+validation is not built).  `dropout=True` is unsupported in 3D (ChapStep raises).
 `args["has_residual"]` (default False) builds the network with residual V-Net blocks (vnet.py:37-67)."""
 import csv
 import logging
@@ -22,7 +23,7 @@ from .networks.net_factory_3d import net_factory_3d
 from .networks.vnet import DualDecoder3d, VNet
 from .synthetic import synthetic_batch_3d
 from .test_3d_patch import var_all_case
-from .train import DEFAULT_ARGS, ChapStep
+from .train import DEFAULT_ARGS, ChapStep, check_num_classes
 
 FLAG_DEFAULTS = dict(DEFAULT_ARGS, model="dualdecoder", num_classes=2, patch_size=[112, 112, 80], batch_size=4, labeled_bs=2,
                      stride_xy=18, stride_z=4, val_interval=200, use_graph=True, gpu=0, seed=1337)
@@ -30,7 +31,7 @@ FLAG_DEFAULTS = dict(DEFAULT_ARGS, model="dualdecoder", num_classes=2, patch_siz
 
 def _synthetic_loader(a):
     lbs, ubs = a["labeled_bs"], a["batch_size"] - a["labeled_bs"]
-    pool = [synthetic_batch_3d(a["seed"] + i, lbs, ubs, *a["patch_size"]) for i in range(4)]
+    pool = [synthetic_batch_3d(a["seed"] + i, lbs, ubs, *a["patch_size"], n_classes=a["num_classes"]) for i in range(4)]
     while True:
         for v, l in pool:
             yield {"image": v, "label": l}
@@ -39,6 +40,7 @@ def _synthetic_loader(a):
 def train(args, snapshot_path):
     a = dict(FLAG_DEFAULTS)
     a.update(args)
+    check_num_classes(a["num_classes"], "chap_amd.train_ours_3D")
     os.makedirs(snapshot_path, exist_ok=True)
     log = logging.getLogger("chap_amd.train3d")
     log.setLevel(logging.INFO)
@@ -72,7 +74,7 @@ def train(args, snapshot_path):
         device_fed = a["use_graph"] and hasattr(loader, "next_into")      # the next batch is built on the device, beside the running iteration
         val = a.get("val_volumes")
         if val is None:
-            vi, vl = synthetic_batch_3d(a["seed"] + 4242, 1, 0, *a["patch_size"])
+            vi, vl = synthetic_batch_3d(a["seed"] + 4242, 1, 0, *a["patch_size"], n_classes=a["num_classes"])
             val = [(vi[0, 0].numpy(), vl[0].numpy())]
         best, captured = 0.0, False
 

@@ -288,7 +288,10 @@ typedef struct { chap_src_t r; float* out; int64_t npix; int64_t pix_per_sample;
 int chap_channel_sum(const chap_chansum_params* p, void* stream);       /* out[c] += sum_pixels a[pixel][c] (fp32, fixed-order partials) */
 
 /* ------------------------------------------------------------------------------------------
- * Segmentation losses on fp32 planar logits [N][C][P]  (train_ours_2D.py:198-216, 319-325). */
+ * Segmentation losses on fp32 planar logits [N][C][P]  (train_ours_2D.py:198-216, 319-325).
+ * Class counts: chap_mix_loss_fwd / _bwd, chap_pseudo_block and chap_kl_fwd_bwd (both modes) are built for every C in 2..8;
+ * chap_mix_loss_multi_fwd / _bwd for C = 2 and C = 4 only.  Any other C returns an error whose message names it ("C=%d");
+ * 9..16 classes are not built (the totals arrays, the inference kernels and the V-Net head route all end at 8). */
 typedef struct {
     const float* logits;        /* [N][C][P]                                                       */
     const int64_t* target_a;    /* [N][P] labels under mask                                        */
@@ -309,7 +312,8 @@ typedef struct {
 int chap_mix_loss_fwd(const chap_mix_loss_params* p, void* stream);
 int chap_mix_loss_bwd(const chap_mix_loss_params* p, void* stream);
 /* Up to four independent terms in one launch per kernel (accumulate, final; backward): bit for bit the results of nterms single-term
- * calls.  Terms may differ in N, mask / target_b being NULL, weights, k_dice / k_ce, accumulate and gscale_dev; C and P are common. */
+ * calls.  Terms may differ in N, mask / target_b being NULL, weights, k_dice / k_ce, accumulate and gscale_dev; C and P are common.
+ * C = 2 or 4 only (the two benchmarked class counts); the callers issue single-term calls for the other counts. */
 typedef struct { int32_t nterms; chap_mix_loss_params term[4]; } chap_mix_loss_multi_params;
 int chap_mix_loss_multi_fwd(const chap_mix_loss_multi_params* p, void* stream);
 int chap_mix_loss_multi_bwd(const chap_mix_loss_multi_params* p, void* stream);
