@@ -274,6 +274,10 @@ class SgdParams(C.Structure):
                 ("grad_scale", _f32), ("n", _i64), ("zero_grad", _i32)]
 
 
+class SgdEmaParams(C.Structure):
+    _fields_ = [("sgd", SgdParams), ("ema", _vp), ("coef", _vp)]
+
+
 _SIGS = {  # name -> (restype, params struct or None)
     "chap_conv_fwd": ConvParams, "chap_pack_weights": PackParams, "chap_conv_c1_fwd": ConvC1Params,
     "chap_conv_c1_bwd": ConvC1BwdParams, "chap_wgrad": WgradParams, "chap_bn_finalize": BnFinalizeParams,
@@ -293,6 +297,8 @@ _SIGS = {  # name -> (restype, params struct or None)
     "chap_mix_loss_multi_fwd": MixLossMultiParams, "chap_mix_loss_multi_bwd": MixLossMultiParams, "chap_bcp_mix": BcpMixParams,
     "chap_residual_fwd": ResidualParams, "chap_residual_bwd": ResidualBwdParams, "chap_grad_sum": GradSumParams,
 }
+# opt-in entry points declared in include/chap_hip_ext.h (same calling convention as _SIGS): not part of the default iteration
+_SIGS_EXT = {"chap_sgd_ema_step": SgdEmaParams}
 _SIZE_FNS = {"chap_pack_size": PackParams, "chap_conv_c1_bwd_ws": ConvC1BwdParams, "chap_wgrad_ws": WgradParams,
              "chap_lcc_ws": LccParams, "chap_metrics_ws": MetricsParams}
 
@@ -343,8 +349,8 @@ def _fn(name):
             fn = getattr(L, name)
         except AttributeError:
             raise ChapError("libchap_hip.so does not export %s (stale build?)" % name)
-        if name in _SIGS:
-            fn.restype, fn.argtypes = C.c_int, [C.POINTER(_SIGS[name]), _vp]
+        if name in _SIGS or name in _SIGS_EXT:
+            fn.restype, fn.argtypes = C.c_int, [C.POINTER(_SIGS.get(name) or _SIGS_EXT[name]), _vp]
         else:
             fn.restype, fn.argtypes = _sz, [C.POINTER(_SIZE_FNS[name])]
         _bound[name] = fn

@@ -321,6 +321,51 @@ extern "C" int chap_sgd_step(const chap_sgd_params* p, void* stream) {
     return CHAP_OK;
 }
 
+// ---- fused SGD + mean-teacher average: sgd_kernel's update, and in the same pass ema = a * ema + b * (the parameter just written) ----
+// (update_ema_variables, train_ours_2D.py:50-54).  The expressions for param / mom / the gradient buckets are sgd_kernel's, token for token: the
+// two kernels write the same bits.  a, b are read from device memory (coef[0], coef[1]) so a captured graph is replayed with new values.
+__global__ void sgd_ema_kernel(const chap_sgd_ema_params Q) {
+    const chap_sgd_params& P = Q.sgd;
+    const float lr = *P.lr;
+    const float ca = Q.coef[0], cb = Q.coef[1];
+    const long n4 = P.n / 4;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        float4 p = ((float4*)P.param)[i], g = ((float4*)P.grad)[i], m = ((float4*)P.mom)[i], e = ((float4*)Q.ema)[i];
+        if (P.grad2) { const float4 h = ((float4*)P.grad2)[i]; g.x += h.x; g.y += h.y; g.z += h.z; g.w += h.w; }
+        CHAP_SGD1(x) CHAP_SGD1(y) CHAP_SGD1(z) CHAP_SGD1(w)
+        e.x = ca * e.x + cb * p.x; e.y = ca * e.y + cb * p.y; e.z = ca * e.z + cb * p.z; e.w = ca * e.w + cb * p.w;
+        ((float4*)P.param)[i] = p; ((float4*)P.mom)[i] = m; ((float4*)Q.ema)[i] = e;
+        if (P.zero_grad) {
+            ((float4*)P.grad)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (P.grad2) ((float4*)P.grad2)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    }
+    if (blockIdx.x == 0) {
+        for (long i = n4 * 4 + threadIdx.x; i < P.n; i += blockDim.x) {
+            const float gr = P.grad[i] + (P.grad2 ? P.grad2[i] : 0.f);
+            const float gg = gr * P.grad_scale + P.weight_decay * P.param[i];
+            const float mm = P.momentum * P.mom[i] + gg;
+            const float pn = P.param[i] - lr * mm;
+            P.mom[i] = mm; P.param[i] = pn;
+            Q.ema[i] = ca * Q.ema[i] + cb * pn;
+            if (P.zero_grad) { P.grad[i] = 0.f; if (P.grad2) P.grad2[i] = 0.f; }
+        }
+    }
+}
+extern "C" int chap_sgd_ema_step(const chap_sgd_ema_params* q, void* stream) {
+    CHAP_CHECK_ARG(q, "chap_sgd_ema_step: null argument");
+    const chap_sgd_params* p = &q->sgd;
+    CHAP_CHECK_ARG(p->param && p->grad && p->mom && p->lr && p->n > 0, "chap_sgd_ema_step: bad argument");
+    CHAP_CHECK_ARG(q->ema, "chap_sgd_ema_step: null ema");
+    CHAP_CHECK_ARG(q->coef, "chap_sgd_ema_step: null coef");
+    CHAP_CHECK_ARG(((uintptr_t)p->param | (uintptr_t)p->grad | (uintptr_t)p->grad2 | (uintptr_t)p->mom | (uintptr_t)q->ema) % 16 == 0, "chap_sgd_ema_step: buffers must be 16-byte aligned");
+    const long n4 = p->n / 4;
+    const int nb = chap_blocks(n4, 2048);
+    hipLaunchKernelGGL(sgd_ema_kernel, dim3(nb > 0 ? nb : 1), dim3(256), 0, (hipStream_t)stream, *q);
+    CHAP_LAUNCH_CHECK("chap_sgd_ema_step");
+    return CHAP_OK;
+}
+
 // ---- GradSim: per output channel, cosine similarity of two gradients of one conv kernel (rows of K contiguous floats) ----
 __global__ __launch_bounds__(256) void gradsim_kernel(const chap_gradsim_params P) {
     const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;

@@ -572,6 +572,17 @@ def sgd_step(param, grad, mom, lr_dev, momentum, weight_decay, grad_scale=1.0, z
     L.call("chap_sgd_step", p, _stream())
 
 
+def sgd_ema_step(param, grad, mom, lr_dev, momentum, weight_decay, ema, coef_dev, grad_scale=1.0, zero_grad=True, grad2=None):
+    """sgd_step and, in the same pass, ema = coef_dev[0] * ema + coef_dev[1] * (the parameter just written): the mean-teacher average
+    (update_ema_variables, train_ours_2D.py:50-54).  param / mom / grad / grad2 get bit for bit what sgd_step writes."""
+    q = L.SgdEmaParams()
+    p = q.sgd
+    p.param, p.grad, p.grad2, p.mom, p.lr = param.data_ptr(), grad.data_ptr(), _p(grad2), mom.data_ptr(), lr_dev.data_ptr()
+    p.momentum, p.weight_decay, p.grad_scale, p.n, p.zero_grad = momentum, weight_decay, grad_scale, param.numel(), int(zero_grad)
+    q.ema, q.coef = _p(ema), _p(coef_dev)
+    L.call("chap_sgd_ema_step", q, _stream())
+
+
 # ------------------------------------------------------------------------------------------
 # inference callers (val_2D.py:54-97, test_3D_util.py:14-79)
 ENSEMBLE_MODES = {"model1": 0, "model2": 1, "logit_ensemble": 2, "prob_ensemble": 3}

@@ -35,16 +35,68 @@ DEFAULT_ARGS = dict(base_lr=0.01, batch_size=24, labeled_bs=12, max_iterations=3
                     momentum=0.9, weight_decay=1e-4, dropout=False, comp_drop=False)
 
 
+def ema_alpha(global_step, decay):
+    """alpha = min(1 - 1 / (global_step + 1), decay) (update_ema_variables, train_ours_2D.py:52), in double: 0 at step 0 (the average starts
+    as a copy of the weights), the plain mean of the weights seen so far during the first 1 / (1 - decay) steps, `decay` from then on."""
+    return min(1.0 - 1.0 / (global_step + 1), decay)
+
+
+def ema_coefficients(global_step, decay):
+    """(a, b) of ema = a * ema + b * param as the kernel reads them: alpha and 1 - alpha, each rounded to fp32 on its own."""
+    alpha = ema_alpha(global_step, decay)
+    f = lambda v: float(torch.tensor(v, dtype=torch.float64).float())
+    return f(alpha), f(1.0 - alpha)
+
+
+def build_teacher(factory):
+    """ema_model = create_model(ema=True) (train_ours_2D.py:238-251): `factory()` -- the call that built the student -- run on a FORK of the torch
+    (host and device), numpy and Python RNG states, which are put back afterwards: the student's run draws the numbers it draws without a
+    teacher.  What the teacher is initialised with does not matter: the first optimizer step overwrites it with the student's weights (alpha = 0)."""
+    import random
+    np_state, py_state = np.random.get_state(), random.getstate()
+    devices = [torch.cuda.current_device()] if torch.cuda.is_available() else []
+    try:
+        with torch.random.fork_rng(devices=devices):
+            teacher = factory()
+    finally:
+        np.random.set_state(np_state)
+        random.setstate(py_state)
+    for p in teacher.parameters():
+        p.requires_grad_(False)                 # param.detach_() (:243-244)
+    return teacher
+
+
 class FusedSGD:
     """optim.SGD(lr, momentum=0.9, weight_decay=1e-4) (train_ours_2D.py:278) as ONE kernel over the
-    model's flat parameter buffer; lr lives in device memory (graph replays pick up new values)."""
+    model's flat parameter buffer; lr lives in device memory (graph replays pick up new values).
 
-    def __init__(self, model, lr, momentum=0.9, weight_decay=1e-4):
+    `ema` (a flat fp32 tensor of the parameter buffer's size: the mean teacher's parameters): the same launch also averages the weights
+    into it, ema = a * ema + b * param (update_ema_variables, :50-54), with (a, b) = `ema_coef`, two fp32 words in device memory that
+    set_ema_step() -- or the owner of the words, ChapStep's schedule block -- fills before every step."""
+
+    def __init__(self, model, lr, momentum=0.9, weight_decay=1e-4, ema=None, ema_decay=0.99):
         self.model, self.momentum, self.weight_decay = model, momentum, weight_decay
         flat, grad = model.flat_buffers()
         self.mom = torch.zeros_like(flat)
         self.lr_dev = torch.full((1,), float(lr), dtype=torch.float32, device=flat.device)
         self.param_groups = [{"lr": float(lr)}]
+        self.ema, self.ema_decay, self.ema_coef, self.ema_model = None, float(ema_decay), None, None
+        if ema is not None:
+            self.set_ema(ema)
+
+    def set_ema(self, ema, model=None):
+        """`model`: the module whose parameters are views of `ema` (its packed weight copies go stale with every step)."""
+        flat = self.model.flat_buffers()[0]
+        if ema.dtype != torch.float32 or ema.shape != flat.shape or ema.device != flat.device or not ema.is_contiguous():
+            raise ValueError("chap_amd FusedSGD: ema must be a contiguous fp32 tensor of the flat parameter buffer's shape %s on %s, got %s %s on %s"
+                             % (tuple(flat.shape), flat.device, ema.dtype, tuple(ema.shape), ema.device))
+        self.ema, self.ema_model = ema, model
+        if self.ema_coef is None:
+            self.ema_coef = torch.tensor([0.0, 1.0], dtype=torch.float32, device=flat.device)
+
+    def set_ema_step(self, global_step):
+        a, b = ema_coefficients(global_step, self.ema_decay)
+        self.ema_coef.copy_(torch.tensor([a, b], dtype=torch.float32))
 
     def set_lr(self, lr):
         self.param_groups[0]["lr"] = float(lr)
@@ -55,7 +107,12 @@ class FusedSGD:
 
     def step(self, grad_scale=1.0, grad2=None):
         flat, grad = self.model.flat_buffers()
-        ops.sgd_step(flat, grad, self.mom, self.lr_dev, self.momentum, self.weight_decay, grad_scale, True, grad2)
+        if self.ema is None:
+            ops.sgd_step(flat, grad, self.mom, self.lr_dev, self.momentum, self.weight_decay, grad_scale, True, grad2)
+        else:
+            ops.sgd_ema_step(flat, grad, self.mom, self.lr_dev, self.momentum, self.weight_decay, self.ema, self.ema_coef, grad_scale, True, grad2)
+            if self.ema_model is not None:
+                self.ema_model.mark_params_dirty()
         self.model.mark_params_dirty()
 
 
@@ -231,7 +288,7 @@ class ChapStep:
     The BCP box offsets, LR and consistency weight live in device memory so that the whole iteration
     can be captured once as a HIP graph (`capture()`) and replayed."""
 
-    def __init__(self, model, args=None, optimizer=None, world_size=1):
+    def __init__(self, model, args=None, optimizer=None, world_size=1, teacher=None):
         a = dict(DEFAULT_ARGS)
         a.update(args or {})
         self.args, self.model = a, model
@@ -240,16 +297,20 @@ class ChapStep:
         dev = self.opt.lr_dev.device
         self.dims = getattr(model, "dims", 2)
         # host-scheduled values of an iteration in ONE device word block -> one host-to-device copy per step:
-        # [BCP box: 4 / 6 int32 | consistency weight f32 | learning rate f32]
+        # [BCP box: 4 / 6 int32 | consistency weight f32 | learning rate f32], and with a mean teacher [| a f32 | b f32] of its average behind them
         nbox = 4 if self.dims == 2 else 6
-        self._sched = torch.zeros(8, dtype=torch.int32, device=dev)
-        self._sched_pin = [torch.empty(8, dtype=torch.int32).pin_memory() for _ in range(4)]      # host side of the schedule block (see _upload_sched)
+        self.teacher = teacher
+        nsched = 8 if teacher is None else 10
+        self._sched = torch.zeros(nsched, dtype=torch.int32, device=dev)
+        self._sched_pin = [torch.empty(nsched, dtype=torch.int32).pin_memory() for _ in range(4)]      # host side of the schedule block (see _upload_sched)
         self._sched_ev, self._sched_k = [None] * 4, 0
         self.box = self._sched[:nbox]
         self.cw_dev = self._sched[6:7].view(torch.float32)
         if isinstance(self.opt, FusedSGD):                       # the optimizer reads its lr from the same block
             self._sched[7:8].view(torch.float32).copy_(self.opt.lr_dev)
             self.opt.lr_dev = self._sched[7:8].view(torch.float32)
+        if teacher is not None:
+            self._attach_teacher(teacher)
         self.iter_num = 0
         self.world_size = world_size
         self.grad_sync = None                   # parallel.DataParallelSync (world_size > 1)
@@ -294,6 +355,44 @@ class ChapStep:
         self._fork_sides, self._fork_mask = {}, 0                   # inside _decoder_fork under capture: {origin stream: forked stream}, CHAP_FORK_MASK
         self._stage_v, self._staged = None, False                   # stage() / stage_from(): made at the first call; a staged batch waits for replay()
 
+    # ------------------------------------------------------------------ mean teacher (train_ours_2D.py:50-54, 238-251: built there, switched off)
+    def _attach_teacher(self, teacher):
+        """`teacher`: a second instance of the student's class, create_model(ema=True) (:238-245).  Its parameters never require grad (:243-244); its
+        flat parameter buffer is what the optimizer kernel averages the student's weights into, with the coefficients in words 8-9 of the
+        schedule block.  It is never run by the iteration: evaluate it after sync_teacher_stats()."""
+        model = self.model
+        if not isinstance(self.opt, FusedSGD):
+            raise ValueError("chap_amd ChapStep: a mean teacher needs the fused optimizer (FusedSGD): its average is part of that kernel")
+        if teacher is model or type(teacher) is not type(model):
+            raise ValueError("chap_amd ChapStep: the teacher must be a second instance of %s, got %s" % (type(model).__name__, type(teacher).__name__))
+        for p in teacher.parameters():
+            p.requires_grad_(False)
+        teacher.set_compute_dtype(model.compute_dtype)
+        model.flat_buffers()
+        teacher._ensure_flat()
+        if [(n, tuple(p.shape)) for n, p in teacher.named_parameters()] != [(n, tuple(p.shape)) for n, p in model.named_parameters()] or teacher._offsets != model._offsets:
+            raise ValueError("chap_amd ChapStep: teacher and student differ in their parameters")
+        self.opt.ema_decay = float(self.args.get("ema_decay", 0.99))
+        self.opt.set_ema(teacher._flat, teacher)
+        self._sched[8:10].view(torch.float32).copy_(torch.tensor([0.0, 1.0]))
+        self.opt.ema_coef = self._sched[8:10].view(torch.float32)
+
+    def sync_teacher_stats(self):
+        """Copy the student's BatchNorm buffers (running_mean, running_var, num_batches_tracked) into the teacher, which also follows the student's
+        compute dtype.  update_ema_variables averages PARAMETERS only and the reference never evaluates its ema model, so what statistics an
+        evaluated teacher normalises with is this build's choice (DESIGN.md "Mean teacher"): the student's current ones.  Call before evaluating."""
+        t = self.teacher
+        if t is None:
+            raise RuntimeError("chap_amd ChapStep: sync_teacher_stats() without a teacher")
+        if t._flat is not self.opt.ema or not t._flat_ok():
+            raise RuntimeError("chap_amd ChapStep: the teacher's parameters were moved off the buffer the optimizer averages into")
+        t.set_compute_dtype(self.model.compute_dtype)
+        src = dict(self.model.named_buffers())
+        with torch.no_grad():
+            for n, b in t.named_buffers():
+                b.copy_(src[n])
+        t.mark_params_dirty()
+
     # ------------------------------------------------------------------ host-side schedule values
     def prepare(self, box_yx=None):
         """Host work of an iteration that must happen BEFORE the device work (and outside a captured
@@ -308,6 +407,8 @@ class ChapStep:
         import struct
         f2i = lambda v: struct.unpack("<i", struct.pack("<f", float(v)))[0]
         vals = list(box_vals) + [0] * (6 - len(box_vals)) + [f2i(cw), f2i(self.opt.param_groups[0]["lr"])]
+        if self.teacher is not None:            # global_step of update_ema_variables (train_ours_2D.py:50-54) = iter_num before finish() counts this step
+            vals += [f2i(c) for c in ema_coefficients(self.iter_num, self.opt.ema_decay)]
         # Through a small ring of PINNED host blocks, asynchronously: a plain `copy_` from pageable memory synchronises the stream,
         # i.e. the host would wait for the previous iteration to drain before it even starts launching the next one (the GPU then
         # idles while the graph's first nodes are being submitted: ~0.5 ms of gaps at the head of every replay in the kernel trace).
@@ -338,13 +439,16 @@ class ChapStep:
         """Everything a long run needs to continue exactly where it stopped.  'model' is the reference's checkpoint
         (what train_ours_2D.py:428-435 saves with torch.save(model.state_dict())); the rest is absent upstream:
         momentum buffer, iteration counter (drives poly LR and the consistency ramp), numpy RNG state (BCP box
-        offsets) and the dropout / VAT noise RNG epoch."""
+        offsets) and the dropout / VAT noise RNG epoch.  With a mean teacher: 'ema', its flat parameter buffer."""
         rng = self.model._rng
-        return {"model": {k: v.detach().clone() for k, v in self.model.state_dict().items()},
+        st = {"model": {k: v.detach().clone() for k, v in self.model.state_dict().items()},
                 "momentum": self.opt.mom.detach().clone(), "iter_num": int(self.iter_num),
                 "lr": float(self.opt.param_groups[0]["lr"]), "numpy_rng": np.random.get_state(),
                 "rng": {"base": rng.base, "count": rng.count, "seed_dev": int(rng.seed_dev.item())},
                 "gradsim": None if self.gradsim is None else [sc.detach().clone() for sc in self.gradsim.get_sim()]}
+        if self.teacher is not None:
+            st["ema"] = self.opt.ema.detach().clone()
+        return st
 
     def load_state_dict(self, st):
         self.model.load_state_dict(st["model"], strict=True)
@@ -359,6 +463,10 @@ class ChapStep:
             for dst, src in zip(self.gradsim.get_sim(), st["gradsim"]):
                 dst.copy_(src)
         self.grad_both.zero_()
+        if self.teacher is not None:            # a checkpoint of a run without a teacher: the average starts at the loaded weights
+            ema = st.get("ema")
+            self.opt.ema.copy_(self.model.flat_buffers()[0] if ema is None else ema)
+            self.teacher.mark_params_dirty()
         return self
 
     # ------------------------------------------------------------------ the device work
@@ -755,6 +863,8 @@ class ChapStep:
         # the optimizer inside the graph changed the weights on the device: the packed copies an EAGER forward
         # (validation, inference, step()) would otherwise reuse are stale -- the graph itself re-packs on every replay
         self.model.mark_params_dirty()
+        if self.teacher is not None:
+            self.teacher.mark_params_dirty()
         self.finish()
         return self._static_out
 

@@ -21,10 +21,11 @@ import torch
 from .inference import test_single_volume
 from .networks.net_factory import net_factory
 from .synthetic import synthetic_batch
-from .train import DEFAULT_ARGS, ChapStep, check_num_classes
+from .train import DEFAULT_ARGS, ChapStep, build_teacher, check_num_classes
 
 FLAG_DEFAULTS = dict(DEFAULT_ARGS, model="dualdecoder", decoder_type="mcnet", gpu=0, seed=1337, image_size=[256, 256],
-                     val_interval=200, labeled_num=7, use_graph=True)          # train_ours_2D.py:469-526
+                     val_interval=200, labeled_num=7, use_graph=True,          # train_ours_2D.py:469-526
+                     mean_teacher=False, ema_decay=0.99)                       # --ema_decay (:499); mean_teacher: the commented-out ema_model (:251)
 
 
 def _synthetic_loader(a):
@@ -48,11 +49,16 @@ def train(args, snapshot_path):
     device = torch.device("cuda", a["gpu"])
     torch.manual_seed(a["seed"])
     np.random.seed(a["seed"])
-    model = net_factory(net_type=a["model"], in_chns=1, class_num=a["num_classes"], device=device, args=a)      # :240
+    make = lambda: net_factory(net_type=a["model"], in_chns=1, class_num=a["num_classes"], device=device, args=a)      # :240
+    model = make()
     model.train()
     if a.get("dtype", "fp32") == "bf16":
         model.set_compute_dtype(torch.bfloat16)
-    step = ChapStep(model, a)
+    if a["mean_teacher"]:                                                        # ema_model = create_model(ema=True) (:238-251)
+        teacher = build_teacher(make).eval()
+        step = ChapStep(model, a, teacher=teacher)
+    else:
+        teacher, step = None, ChapStep(model, a)
     loader = a.get("trainloader")
     if loader is None and a.get("root_path") and a.get("labeled_slices"):
         from .data import DeviceLoader, SliceStore
@@ -65,7 +71,12 @@ def train(args, snapshot_path):
     if val is None:
         vi, vl = synthetic_batch(a["seed"] + 4242, 8, 0, *a["image_size"], a["num_classes"])
         val = [(vi[:, 0].unsqueeze(0), vl.unsqueeze(0))]
-    best, captured = 0.0, False
+    best, ema_best, captured = 0.0, -1.0, False         # (the first validated teacher is the best so far, whatever it scores)
+
+    def validate(net):
+        metric = sum(np.array(test_single_volume(im, lb, net, classes=a["num_classes"], patch_size=a["image_size"],
+                                                 model_type="logit_ensemble", device=device)) for im, lb in val) / len(val)
+        return float(np.mean(metric, axis=0)[0]), float(np.mean(metric, axis=0)[1])
 
     def batches():
         """The epoch loop of the reference (:299-302, 459-463): `max_epoch = max_iterations // len(trainloader) + 1` passes
@@ -96,10 +107,7 @@ def train(args, snapshot_path):
             log.info("iteration %d : bcp loss : %f vat loss : %f" % (it, sum(float(l[2]) for l in out["mix_losses"]), float(out["vat_loss"])))
         if it > 0 and it % a["val_interval"] == 0:                               # :407-456
             model.eval()
-            metric = sum(np.array(test_single_volume(im, lb, model, classes=a["num_classes"], patch_size=a["image_size"],
-                                                     model_type="logit_ensemble", device=device)) for im, lb in val) / len(val)
-            performance = float(np.mean(metric, axis=0)[0])
-            mean_hd95 = float(np.mean(metric, axis=0)[1])
+            performance, mean_hd95 = validate(model)
             torch.save(model.state_dict(), os.path.join(snapshot_path, "latest.pth"))
             if performance > best:
                 best = performance
@@ -107,6 +115,14 @@ def train(args, snapshot_path):
                 with open(os.path.join(snapshot_path, "val.csv"), "a", newline="") as f:
                     csv.writer(f).writerow([time.strftime("%Y-%m-%d %H:%M:%S"), it, round(best, 4)])
             log.info("iteration %d : model1_mean_dice : %f model1_mean_hd95 : %f" % (it, performance, mean_hd95))      # :453-454
+            if teacher is not None:             # the averaged weights with the student's current BatchNorm statistics, after the student, same function
+                step.sync_teacher_stats()
+                ema_dice, ema_hd95 = validate(teacher)
+                torch.save(teacher.state_dict(), os.path.join(snapshot_path, "ema_latest.pth"))
+                if ema_dice > ema_best:
+                    ema_best = ema_dice
+                    torch.save(teacher.state_dict(), os.path.join(snapshot_path, "{}_ema_best_model.pth".format(a["model"])))
+                log.info("iteration %d : ema_mean_dice : %f ema_mean_hd95 : %f" % (it, ema_dice, ema_hd95))
             model.train()
         if it >= a["max_iterations"]:
             break

@@ -23,10 +23,11 @@ from .networks.net_factory_3d import net_factory_3d
 from .networks.vnet import DualDecoder3d, VNet
 from .synthetic import synthetic_batch_3d
 from .test_3d_patch import var_all_case
-from .train import DEFAULT_ARGS, ChapStep, check_num_classes
+from .train import DEFAULT_ARGS, ChapStep, build_teacher, check_num_classes
 
 FLAG_DEFAULTS = dict(DEFAULT_ARGS, model="dualdecoder", num_classes=2, patch_size=[112, 112, 80], batch_size=4, labeled_bs=2,
-                     stride_xy=18, stride_z=4, val_interval=200, use_graph=True, gpu=0, seed=1337)
+                     stride_xy=18, stride_z=4, val_interval=200, use_graph=True, gpu=0, seed=1337,
+                     mean_teacher=False, ema_decay=0.99)       # as train_ours_2D: --ema_decay (train_ours_2D.py:499), the ema_model of :251
 
 
 def _synthetic_loader(a):
@@ -50,20 +51,26 @@ def train(args, snapshot_path):
         device = torch.device("cuda", a["gpu"])
         torch.manual_seed(a["seed"])
         np.random.seed(a["seed"])
-        if a.get("has_residual", False):
-            # ResidualConvBlock nets (vnet.py:37-67): net_factory_3d keeps the reference's signature, which has no such flag, so the class is built
-            # here with the factory's train-mode arguments
-            cls = {"vnet": VNet, "dualdecoder": DualDecoder3d}.get(a["model"])
-            kw = dict(args=a) if cls is DualDecoder3d else {}
-            model = cls(n_channels=1, n_classes=a["num_classes"], normalization="batchnorm", has_dropout=True, has_residual=True, **kw).to(device) if cls else None
-        else:
-            model = net_factory_3d(net_type=a["model"], in_chns=1, class_num=a["num_classes"], mode="train", device=device, args=a)
+        def make():
+            if a.get("has_residual", False):
+                # ResidualConvBlock nets (vnet.py:37-67): net_factory_3d keeps the reference's signature, which has no such flag, so the class is built
+                # here with the factory's train-mode arguments
+                cls = {"vnet": VNet, "dualdecoder": DualDecoder3d}.get(a["model"])
+                kw = dict(args=a) if cls is DualDecoder3d else {}
+                return cls(n_channels=1, n_classes=a["num_classes"], normalization="batchnorm", has_dropout=True, has_residual=True, **kw).to(device) if cls else None
+            return net_factory_3d(net_type=a["model"], in_chns=1, class_num=a["num_classes"], mode="train", device=device, args=a)
+
+        model = make()
         if model is None:
             raise ValueError("chap_amd.train_ours_3D: no 3D network named %r" % (a["model"],))
         model.train()
         if a.get("dtype", "fp32") == "bf16":
             model.set_compute_dtype(torch.bfloat16)
-        step = ChapStep(model, a)
+        if a["mean_teacher"]:                   # ema_model = create_model(ema=True) (train_ours_2D.py:238-251)
+            teacher = build_teacher(make).eval()
+            step = ChapStep(model, a, teacher=teacher)
+        else:
+            teacher, step = None, ChapStep(model, a)
         loader = a.get("trainloader")
         if loader is None and a.get("root_path") and a.get("labeled_num"):
             from .data import DeviceLoader, VolumeStore
@@ -76,7 +83,7 @@ def train(args, snapshot_path):
         if val is None:
             vi, vl = synthetic_batch_3d(a["seed"] + 4242, 1, 0, *a["patch_size"], n_classes=a["num_classes"])
             val = [(vi[0, 0].numpy(), vl[0].numpy())]
-        best, captured = 0.0, False
+        best, ema_best, captured = 0.0, -1.0, False         # (the first validated teacher is the best so far, whatever it scores)
 
         def batches():
             """train_ours_2D.py:299-302, 459-463: a finite loader is re-iterated until max_iterations is reached; one that yields nothing ends
@@ -114,6 +121,14 @@ def train(args, snapshot_path):
                     with open(os.path.join(snapshot_path, "val.csv"), "a", newline="") as f:
                         csv.writer(f).writerow([time.strftime("%Y-%m-%d %H:%M:%S"), it, round(best, 4)])
                 log.info("iteration %d : dice_score : %f" % (it, dice))
+                if teacher is not None:         # the averaged weights with the student's current BatchNorm statistics, after the student, same function
+                    step.sync_teacher_stats()
+                    ema_dice = float(var_all_case(teacher, val, a["num_classes"], tuple(a["patch_size"]), a["stride_xy"], a["stride_z"]))
+                    torch.save(teacher.state_dict(), os.path.join(snapshot_path, "ema_latest.pth"))
+                    if ema_dice > ema_best:
+                        ema_best = ema_dice
+                        torch.save(teacher.state_dict(), os.path.join(snapshot_path, "{}_ema_best_model.pth".format(a["model"])))
+                    log.info("iteration %d : ema_dice_score : %f" % (it, ema_dice))
                 model.train()
             if it >= a["max_iterations"]:
                 break

@@ -664,6 +664,9 @@ int chap_debug_copy(const void* src, void* dst, int64_t bytes, int32_t blocks, v
 const char* chap_last_error(void);
 int chap_abi_version(void);
 
+/* Opt-in entry points added to ABI 9 without a version change (nothing above depends on them): the mean teacher's optimizer step. */
+#include "chap_hip_ext.h"
+
 #ifdef __cplusplus
 }
 #endif
