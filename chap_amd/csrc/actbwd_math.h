@@ -7,16 +7,17 @@
 
 typedef float actbwd_f32x2 __attribute__((ext_vector_type(2)));
 
-// per-channel constants of 8 channels from the totals S0 = sum dz, S1 = sum dz*xhat
+// per-channel constants from the totals S0 = sum dz, S1 = sum dz*xhat: of one channel, of 8
+__device__ __forceinline__ void actbwd_consts1(float a0, float a1, float gm, float mean, float istd, float count, float& k0, float& cB, float& cC) {
+    k0 = gm * istd;
+    const float k1 = a0 / count, k2 = a1 / count;
+    cB = -istd * k0 * k2;
+    cC = __builtin_fmaf(mean * istd * k0, k2, -k0 * k1);
+}
 __device__ __forceinline__ void actbwd_consts8(const float a0[8], const float a1[8], const float gm[8], const float mean[8], const float istd[8], float count,
                                                float k0[8], float cB[8], float cC[8]) {
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        k0[j] = gm[j] * istd[j];
-        const float k1 = a0[j] / count, k2 = a1[j] / count;
-        cB[j] = -istd[j] * k0[j] * k2;
-        cC[j] = __builtin_fmaf(mean[j] * istd[j] * k0[j], k2, -k0[j] * k1);
-    }
+    for (int j = 0; j < 8; ++j) actbwd_consts1(a0[j], a1[j], gm[j], mean[j], istd[j], count, k0[j], cB[j], cC[j]);
 }
 
 // dz = dy * d(activation)/dz of 8 channels (packed fp32: v_pk_fma_f32 / v_pk_mul_f32)

@@ -19,6 +19,42 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
     return v;
 }
 
+// A kernel's argument block read ONCE, in front of everything else: every word is pinned to a scalar register here, so the compiler cannot
+// sink the scalar loads next to their uses (it does, and each group of them is then one more dependent wait in front of the first load).
+// Cost: the whole block sits in scalar registers at the top (50 to 60 of them: act_bwd 49-65 -> 74-84 SGPRs, bn_finalize 56 -> 70, of 102), so only for
+// kernels with room.  The argument structs have padding (after `ng` in chap_act_bwd_params): the bit cast copies those bytes as whatever the launch
+// put there, nothing reads them, and the cast back leaves them padding again; formally their value is indeterminate, which is why no
+// has_unique_object_representations assert can stand here.
+template <typename A>
+__device__ __forceinline__ A chap_args_once(const A& p) {
+    static_assert(sizeof(A) % 4 == 0, "argument block is not a whole number of words");
+    struct words { uint32_t w[sizeof(A) / 4]; };
+    words w = __builtin_bit_cast(words, p);
+#pragma unroll
+    for (unsigned i = 0; i < sizeof(A) / 4; ++i) asm volatile("" : "+s"(w.w[i]));
+    return __builtin_bit_cast(A, w);
+}
+// ... a pointer that went through a register pin is a generic one to the compiler (flat loads and stores: both wait counters): the kernel
+// says that it is global where it uses it
+#define CHAP_GLOBAL __attribute__((address_space(1)))
+typedef const CHAP_GLOBAL char* chap_gptr;
+typedef float f32x4n __attribute__((ext_vector_type(4)));         // native vectors: the HIP vector classes have no members for a qualified address space
+typedef uint32_t u32x4n __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2n __attribute__((ext_vector_type(2)));
+template <typename X> __device__ __forceinline__ chap_gptr chap_global(const X* p) { return (chap_gptr)p; }
+template <typename V> __device__ __forceinline__ V ldg(chap_gptr p) { return *(const CHAP_GLOBAL V*)p; }
+__device__ __forceinline__ void ld8g(chap_gptr p, float v[8]) {
+    const f32x4n a = ldg<f32x4n>(p), b = ldg<f32x4n>(p + 16);
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+}
+__device__ __forceinline__ void st8g(CHAP_GLOBAL float* p, const float v[8]) {
+    *(CHAP_GLOBAL f32x4n*)p = f32x4n{v[0], v[1], v[2], v[3]};
+    *(CHAP_GLOBAL f32x4n*)(p + 4) = f32x4n{v[4], v[5], v[6], v[7]};
+}
+__device__ __forceinline__ void st8g(CHAP_GLOBAL bf16_t* p, const float v[8]) {
+    *(CHAP_GLOBAL u32x4n*)p = u32x4n{pack2bf(v[0], v[1]), pack2bf(v[2], v[3]), pack2bf(v[4], v[5]), pack2bf(v[6], v[7])};
+}
+
 // =========================================================================================
 // First conv, Cin = 1, k3 s1 "same" (unet.py:50 with in_chns=1; vnet.py:19 with n_channels=1).
 // One thread per output pixel computes all Cout (<= 32) channels; weights + bias live in LDS.
@@ -251,19 +287,21 @@ extern "C" int chap_conv_c1_bwd(const chap_conv_c1_bwd_params* p, void* stream) 
 // One wave per channel: lane l sums slots l, l+64, ... (and the sub-lattice rows of a transposed conv) in fp64, then a
 // fixed xor butterfly -- the same order on every run.  mean = c + S/n, var = Q/n - (S/n)^2 with the moments taken about
 // the conv's shift c (no cancellation once c tracks the mean), evaluated in fp64.
-__device__ __forceinline__ void bn_finalize_kernel(const chap_bn_finalize_params& P) {
+__device__ __forceinline__ void bn_finalize_kernel(const chap_bn_finalize_params& Pk) {
+    const chap_bn_finalize_params P = chap_args_once(Pk);       // one scalar load and wait in front of the kernel instead of six
+    typedef const CHAP_GLOBAL float* gf;
     const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (c >= P.C) return;
     // slots in use: the header word the producing conv wrote (a host-side note of the conv's grid was tried in round 3 to save this
     // load: no measurable difference, and a hidden coupling between two calls -- removed)
-    const int nslots = *(const int*)P.stats;
+    const int nslots = *(const CHAP_GLOBAL int*)P.stats;
     // the per-channel parameters are requested NOW, next to the header and the slots: behind the reduction they were a third
     // dependent memory round trip of a kernel that is nothing but latency
     const bool upd = P.momentum > 0.f && P.running_mean;
-    const float gam = P.gamma[c], bet = P.beta[c], sft = P.stats_shift ? P.stats_shift[c] : 0.f;
-    const float rm0 = upd ? P.running_mean[c] : 0.f, rv0 = upd ? P.running_var[c] : 0.f;
+    const float gam = ((gf)P.gamma)[c], bet = ((gf)P.beta)[c], sft = P.stats_shift ? ((gf)P.stats_shift)[c] : 0.f;
+    const float rm0 = upd ? ((gf)P.running_mean)[c] : 0.f, rv0 = upd ? ((gf)P.running_var)[c] : 0.f;
     const int nsub = P.Clog / P.C;
-    const float* st = P.stats + CHAP_STATS_HDR;
+    const gf st = (gf)P.stats + CHAP_STATS_HDR;
     double s = 0.0, q = 0.0;
     // a lane's slots are lane, lane + 64, ...: at most CHAP_STATS_MAX_SLOTS / 64 = 16 of them.  All loads of a batch are issued
     // before the first add (the kernel is pure latency: one dependent load per iteration made it 6.7 us), the adds keep the
@@ -274,7 +312,7 @@ __device__ __forceinline__ void bn_finalize_kernel(const chap_bn_finalize_params
 #pragma unroll
         for (int i = 0; i < NB; ++i) {
             const int b = lane + 64 * i;
-            const float* row = st + (long)(b < nslots ? b : 0) * 2 * P.Clog + k * P.C + c;
+            const gf row = st + (long)(b < nslots ? b : 0) * 2 * P.Clog + k * P.C + c;
             vs[i] = row[0]; vq[i] = row[P.Clog];
         }
 #pragma unroll
@@ -285,7 +323,7 @@ __device__ __forceinline__ void bn_finalize_kernel(const chap_bn_finalize_params
     }
     s = wave_sum_f64(s); q = wave_sum_f64(q);
     if (lane != 0) return;
-    if (c == 0 && P.num_batches_tracked && P.momentum > 0.f) *P.num_batches_tracked += 1;
+    if (c == 0 && P.num_batches_tracked && P.momentum > 0.f) *(CHAP_GLOBAL int64_t*)P.num_batches_tracked += 1;
     const double cnt = (double)P.count;
     const double ms = s / cnt;                                   // mean of (x - shift)
     double var = q / cnt - ms * ms;
@@ -293,13 +331,14 @@ __device__ __forceinline__ void bn_finalize_kernel(const chap_bn_finalize_params
     const float mean = (float)((double)sft + ms);
     const float invstd = (float)(1.0 / sqrt(var + (double)P.eps));
     const float sc = gam * invstd;
-    P.scale[c] = sc;
-    P.shift[c] = bet - mean * sc;
-    if (P.mean) { P.mean[c] = mean; P.invstd[c] = invstd; }
+    typedef CHAP_GLOBAL float* gw;
+    ((gw)P.scale)[c] = sc;
+    ((gw)P.shift)[c] = bet - mean * sc;
+    if (P.mean) { ((gw)P.mean)[c] = mean; ((gw)P.invstd)[c] = invstd; }
     if (upd) {
         const float unb = (float)(cnt > 1.0 ? var * cnt / (cnt - 1.0) : var);
-        P.running_mean[c] = (1.f - P.momentum) * rm0 + P.momentum * mean;
-        P.running_var[c] = (1.f - P.momentum) * rv0 + P.momentum * unb;
+        ((gw)P.running_mean)[c] = (1.f - P.momentum) * rm0 + P.momentum * mean;
+        ((gw)P.running_var)[c] = (1.f - P.momentum) * rv0 + P.momentum * unb;
     }
 }
 extern "C" int chap_bn_finalize(const chap_bn_finalize_params* p, void* stream) {
@@ -573,105 +612,234 @@ extern "C" int chap_upsample2x_bwd(const chap_upsample_bwd_params* p, void* stre
 // Thread = (pixel, 8 channels); a block covers 256/C8 pixels per step, grid-stride; per-channel
 // partial sums are reduced over the block in a fixed order and stored as this block's partial row
 // (sums layout: [1 + CHAP_ACT_BWD_SLOTS][2][C], row 0 = totals written by act_bwd_sum_kernel).
+//
+// How a thread asks for its data (the arithmetic and the order of every sum are those of actbwd_math.h and never depend on it):
+//  * the kernel arguments are copied into an act_plan ONCE, in front of everything: byte base, byte stride and presence of every source;
+//  * all loads of a trip are requested together, with no branch between them (the rule noted in halo_commit_impl, conv_kernel.h): a source
+//    the layer does not have (gradients 1 and 2, pooled gradient and index, keep mask, channel multipliers) points at the 16 bytes of the raw
+//    load of the same trip -- a valid address that is in the cache already -- and its value is never used.  The raw load goes LAST: loads
+//    return in order, so the wait in front of the first use of a trip covers the whole trip;
+//  * the next trip is requested as soon as the current one is consumed.  The pixel of the request is clamped to the last one, so a lane past
+//    the end (the ragged last trip) asks for an address inside the tensors;
+//  * GEN = false is the layer with exactly one incoming gradient and neither pooled gradient nor channel multipliers (21 of the 26
+//    BatchNorm layers of the 2D step): it requests raw, that gradient and the keep mask only.  GEN = true takes every layer;
+//  * reduce: the per-channel constants and the first trip go out together, one memory round trip in front of the loop (the general fp32
+//    instance: two).  apply: two (see the prologue of act_bwd_kernel for both).
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
+template <typename T> struct act_pk;                        // 8 channels as loaded
+template <> struct act_pk<bf16_t> { u32x4n v; };
+template <> struct act_pk<float> { f32x4n a, b; };
+__device__ __forceinline__ void pk_ld(chap_gptr p, act_pk<bf16_t>& r) { r.v = ldg<u32x4n>(p); }
+__device__ __forceinline__ void pk_ld(chap_gptr p, act_pk<float>& r) { r.a = ldg<f32x4n>(p); r.b = ldg<f32x4n>(p + 16); }
+__device__ __forceinline__ void pk_unpack(const act_pk<bf16_t>& r, float v[8]) {      // the conversions of ld8 (common.h)
+    v[0] = __uint_as_float(r.v.x << 16); v[1] = __uint_as_float(r.v.x & 0xffff0000u);
+    v[2] = __uint_as_float(r.v.y << 16); v[3] = __uint_as_float(r.v.y & 0xffff0000u);
+    v[4] = __uint_as_float(r.v.z << 16); v[5] = __uint_as_float(r.v.z & 0xffff0000u);
+    v[6] = __uint_as_float(r.v.w << 16); v[7] = __uint_as_float(r.v.w & 0xffff0000u);
+}
+__device__ __forceinline__ void pk_unpack(const act_pk<float>& r, float v[8]) {
+    v[0] = r.a.x; v[1] = r.a.y; v[2] = r.a.z; v[3] = r.a.w; v[4] = r.b.x; v[5] = r.b.y; v[6] = r.b.z; v[7] = r.b.w;
+}
+
+struct act_src1 { chap_gptr base; u32 stride; };         // bytes; element i of the source sits at base + i * stride + (the lane's channel offset), all of it below 2^32
+// wave-uniform: lives in scalar registers
+struct act_plan {
+    act_src1 raw, g[3], gp, idx, keep, cm;
+    bool has_g[3], has_pool, has_keep, has_cm, need_coords, act;
+    int cm_hi;                                              // byte offset of channels 4..7 of the multipliers (0 when they alias the raw load)
+    int W, H, D;
+    float slope, keep_scale;
+};
 template <typename T>
-__device__ __forceinline__ void act_bwd_dz(const chap_act_bwd_params& P, const float sa[8], const float sb[8], int n, long pix, int y, int x, int c8,
-                                           float raw[8], float dz[8]) {
-    const chap_src_t& s = P.r;
-    const int C = s.C;
-    ld8((const T*)s.ptr + pix * s.ld + s.coff + c8, raw);
-    float gsum[8];
+__device__ __forceinline__ act_plan act_make_plan(const chap_act_bwd_params& P) {
+    constexpr u32 ES = sizeof(T);
+    act_plan S;
+    const u32 C = (u32)P.r.C;
+    S.raw = {chap_global(P.r.ptr) + (long)P.r.coff * ES, (u32)P.r.ld * ES};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        S.has_g[k] = k < P.ng;
+        S.g[k] = S.has_g[k] ? act_src1{chap_global(P.g[k]) + (long)P.g_coff[k] * ES, (u32)P.g_ld[k] * ES} : S.raw;
+    }
+    S.has_pool = P.g_pool != nullptr; S.has_keep = P.r.keep != nullptr; S.has_cm = P.r.chan_mul != nullptr;
+    S.gp = S.has_pool ? act_src1{chap_global(P.g_pool), C * ES} : S.raw;
+    S.idx = S.has_pool ? act_src1{chap_global(P.pool_idx), C} : S.raw;
+    S.keep = S.has_keep ? act_src1{chap_global(P.r.keep), C} : S.raw;
+    S.cm = S.has_cm ? act_src1{chap_global(P.r.chan_mul), C * 4} : S.raw;
+    S.cm_hi = S.has_cm ? 16 : 0;
+    S.need_coords = S.has_pool || S.has_cm;
+    S.act = P.r.act != 0;
+    S.W = P.W; S.H = P.H; S.D = P.D;
+    S.slope = P.r.slope; S.keep_scale = P.r.keep_scale;
+    return S;
+}
+// the lane's channel offset in bytes: of the element type (raw, gradients), of the byte masks (an absent mask reads the first 8 bytes
+// of the lane's own raw unit or of an earlier one: c8 <= c8 * sizeof(T)), of the multipliers
+struct act_lane { int t, b, cm; };
+
+template <typename T> struct act_trip { act_pk<T> raw, g0, g1, g2, gp; u32x2n idx, keep; f32x4n cm0, cm1; uint32_t me; };
+
+__device__ __forceinline__ chap_gptr act_addr(const act_src1& s, u32 i, int lane) { return s.base + (u32)(i * s.stride + (u32)lane); }      // scalar base + 32-bit lane offset: no 64-bit address kept or computed per lane (the entry points check the 4 GB this assumes)
+template <typename T, bool GEN>
+__device__ __forceinline__ void act_issue(const act_plan& S, const act_lane& L, u32 pix, act_trip<T>& t) {
+    if (GEN) {
+        u32 pidx = pix, nidx = pix;
+        t.me = 0;
+        if (S.need_coords) {                       // wave-uniform, no load inside: only the pooled gradient / Dropout3d path needs (n, y, x)
+            const u32 up = pix;
+            const int x = (int)(up % (u32)S.W); u32 r = up / (u32)S.W;
+            const int y = (int)(r % (u32)S.H); r /= (u32)S.H;
+            const int n = (int)(r / (u32)S.D);
+            const int OH = S.H / 2, OW = S.W / 2;
+            const u32 pp = ((u32)n * OH + (y >> 1)) * OW + (x >> 1);
+            t.me = ((y & 1) << 1) | (x & 1);
+            pidx = S.has_pool ? pp : pix; nidx = S.has_cm ? (u32)n : pix;
+        }
+        pk_ld(act_addr(S.g[0], pix, L.t), t.g0);
+        pk_ld(act_addr(S.g[1], pix, L.t), t.g1);
+        pk_ld(act_addr(S.g[2], pix, L.t), t.g2);
+        pk_ld(act_addr(S.gp, pidx, L.t), t.gp);
+        t.idx = ldg<u32x2n>(act_addr(S.idx, pidx, L.b));
+        const chap_gptr cp = act_addr(S.cm, nidx, L.cm);
+        t.cm0 = ldg<f32x4n>(cp); t.cm1 = ldg<f32x4n>(cp + S.cm_hi);
+    } else {
+        pk_ld(act_addr(S.g[0], pix, L.t), t.g0);
+    }
+    t.keep = ldg<u32x2n>(act_addr(S.keep, pix, L.b));
+    pk_ld(act_addr(S.raw, pix, L.t), t.raw);
+}
+
+// the incoming gradient of one trip: ((0 + g0) + g1) + g2, then the routed pooled gradient
+template <typename T, bool GEN>
+__device__ __forceinline__ void act_gsum(const act_plan& S, const act_trip<T>& t, float gsum[8]) {
+    float v[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) gsum[j] = 0.f;
-    for (int k = 0; k < P.ng; ++k) {
-        float v[8];
-        ld8((const T*)P.g[k] + pix * P.g_ld[k] + P.g_coff[k] + c8, v);
+    if (!GEN || S.has_g[0]) {
+        pk_unpack(t.g0, v);
 #pragma unroll
         for (int j = 0; j < 8; ++j) gsum[j] += v[j];
     }
-    if (P.g_pool) {
-        const int OH = P.H / 2, OW = P.W / 2;
-        const long pp = ((long)n * OH + (y >> 1)) * OW + (x >> 1);
-        const uint32_t me = ((y & 1) << 1) | (x & 1);
-        float v[8];
-        ld8((const T*)P.g_pool + pp * C + c8, v);
-        const uint2 m = *(const uint2*)(P.pool_idx + pp * C + c8);
+    if (GEN) {
+        if (S.has_g[1]) {
+            pk_unpack(t.g1, v);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const uint32_t w = j < 4 ? m.x : m.y;
-            if (((w >> (8 * (j & 3))) & 0xff) == me) gsum[j] += v[j];
+            for (int j = 0; j < 8; ++j) gsum[j] += v[j];
+        }
+        if (S.has_g[2]) {
+            pk_unpack(t.g2, v);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) gsum[j] += v[j];
+        }
+        if (S.has_pool) {
+            pk_unpack(t.gp, v);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const uint32_t w = j < 4 ? t.idx.x : t.idx.y;
+                if (((w >> (8 * (j & 3))) & 0xff) == t.me) gsum[j] += v[j];
+            }
         }
     }
-    // a = keep*ks*cm*leaky(z), z = scale*raw+shift  ->  da/dz = keep*ks*cm*(z>0 ? 1 : slope)      (actbwd_math.h)
-    actbwd_deriv8(raw, gsum, sa, sb, s.act != 0, s.slope, dz);
-    if (s.keep) actbwd_keep8(dz, *(const uint2*)(s.keep + pix * C + c8), s.keep_scale);
-    if (s.chan_mul) {
-        float cm[8];
-        ld8(s.chan_mul + (long)n * C + c8, cm);
+}
+// ... and dz from it: a = keep*ks*cm*leaky(z), z = scale*raw+shift  ->  da/dz = keep*ks*cm*(z>0 ? 1 : slope)      (actbwd_math.h)
+template <typename T, bool GEN>
+__device__ __forceinline__ void act_bwd_dz(const act_plan& S, const act_trip<T>& t, const float gsum[8], const float sa[8], const float sb[8], float raw[8], float dz[8]) {
+    pk_unpack(t.raw, raw);
+    actbwd_deriv8(raw, gsum, sa, sb, S.act, S.slope, dz);
+    if (S.has_keep) actbwd_keep8(dz, make_uint2(t.keep.x, t.keep.y), S.keep_scale);
+    if (GEN && S.has_cm) {
+        const float cm[8] = {t.cm0.x, t.cm0.y, t.cm0.z, t.cm0.w, t.cm1.x, t.cm1.y, t.cm1.z, t.cm1.w};
 #pragma unroll
         for (int j = 0; j < 8; ++j) dz[j] *= cm[j];
     }
 }
 
-template <typename T, bool APPLY>
-__device__ __forceinline__ void act_bwd_kernel(const chap_act_bwd_params& P) {
-    extern __shared__ float red[];            // reduce phase: [4 waves][2][C] partials; apply phase: [2][C] totals
-    const int C = P.r.C, C8 = C / 8;
+template <typename T, bool APPLY, bool GEN>
+__device__ __forceinline__ void act_bwd_kernel(const chap_act_bwd_params& Pk) {
+    extern __shared__ float red[];            // reduce phase: [4 waves][2][C] partials
+    // ---- the kernel arguments, once ----
+    const chap_act_bwd_params P = chap_args_once(Pk);
+    const act_plan S = act_make_plan<T>(P);
+    const int C = P.r.C, C8 = C / 8, bn = P.bn;
     const long npix = (long)P.N * P.D * P.H * P.W;
+    const chap_gptr scale = chap_global(P.r.scale), shift = chap_global(P.r.shift);
+    const chap_gptr meanp = chap_global(P.mean), istdp = chap_global(P.invstd), gammap = chap_global(P.gamma);
+    CHAP_GLOBAL float* const sums = (CHAP_GLOBAL float*)P.sums; CHAP_GLOBAL T* const gout = (CHAP_GLOBAL T*)P.gout;
+    const float count = P.count;
     const int c8 = (threadIdx.x % C8) * 8;
-    const int prow = threadIdx.x / C8, PPB = 256 / C8;      // C8 in {2,4,8,...,32} divides 256
-    float s0[8], s1[8], mean[8], istd[8], k0[8], sa[8], sb[8], cB[8], cC[8], cM[8];
+    float s0[8], s1[8], istd[8], k0[8], sa[8], sb[8], cB[8], cC[8], cM[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { s0[j] = 0.f; s1[j] = 0.f; sa[j] = 1.f; sb[j] = 0.f; }
-    if (P.r.scale) { ld8(P.r.scale + c8, sa); ld8(P.r.shift + c8, sb); }      // per-channel constants: loaded once
+    for (int j = 0; j < 8; ++j) { s0[j] = 0.f; s1[j] = 0.f; sa[j] = 1.f; sb[j] = 0.f; k0[j] = 1.f; istd[j] = 1.f; cB[j] = 0.f; cC[j] = 0.f; cM[j] = 0.f; }
+    // (first of all: while these loads and divisions are in flight nothing else of the thread is in registers yet)
+    if (APPLY && bn == 1) {                            // training-mode BatchNorm backward
+        float mean[8], gm[8], a0[8], a1[8];
+        ld8g(meanp + c8 * 4, mean); ld8g(istdp + c8 * 4, istd); ld8g(gammap + c8 * 4, gm);
+        ld8g((chap_gptr)(sums + c8), a0); ld8g((chap_gptr)(sums + C + c8), a1);
+        // g = k0*(dz - k1 - xhat*k2), xhat = raw*istd - mean*istd  ==  dz*k0 + raw*cB + cC  (two FMAs per element; actbwd_math.h)
+        // one channel at a time: the scheduler interleaves all 16 divisions otherwise, and their temporaries are the kernel's register peak
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { k0[j] = 1.f; mean[j] = 0.f; istd[j] = 1.f; }
-    if (P.bn) { ld8(P.mean + c8, mean); ld8(P.invstd + c8, istd); }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { cB[j] = 0.f; cC[j] = 0.f; cM[j] = -mean[j] * istd[j]; }      // xhat = raw*istd + cM
-    if (APPLY) {
-        if (P.bn == 1) {                               // training-mode BatchNorm backward
-            for (int i = threadIdx.x; i < 2 * C; i += 256) red[i] = P.sums[i];      // totals in row 0 (written by act_bwd_sum_kernel together with dgamma / dbeta)
-            __syncthreads();
-            float gm[8], a0[8], a1[8];
-            ld8(P.gamma + c8, gm);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { a0[j] = red[c8 + j]; a1[j] = red[C + c8 + j]; }
-            // g = k0*(dz - k1 - xhat*k2), xhat = raw*istd - mean*istd  ==  dz*k0 + raw*cB + cC  (two FMAs per element; actbwd_math.h)
-            actbwd_consts8(a0, a1, gm, mean, istd, P.count, k0, cB, cC);
-        } else if (P.r.scale) {                        // fixed affine (eval-mode BN): dz/draw = scale
-            ld8(P.r.scale + c8, k0);
+        for (int j = 0; j < 8; ++j) {
+            actbwd_consts1(a0[j], a1[j], gm[j], mean[j], istd[j], count, k0[j], cB[j], cC[j]);
+            __builtin_amdgcn_sched_barrier(0);                 // (the last one also keeps the loads below from being hoisted over this)
         }
     }
-    const bool need_coords = P.g_pool != nullptr || P.r.chan_mul != nullptr;
-    if (prow < PPB) {
-        for (long pix = (long)blockIdx.x * PPB + prow; pix < npix; pix += (long)gridDim.x * PPB) {
-            int x = 0, y = 0, n = 0;
-            if (need_coords) {                     // wave-uniform: only the pooled gradient / Dropout3d path needs (n, y, x)
-                const u32 up = (u32)pix;
-                x = (int)(up % (u32)P.W); u32 r = up / (u32)P.W;
-                y = (int)(r % (u32)P.H); r /= (u32)P.H;
-                n = (int)(r / (u32)P.D);
-            }
-            float raw[8], dz[8];
-            act_bwd_dz<T>(P, sa, sb, n, pix, y, x, c8, raw, dz);
-            if (!APPLY) {
+    const int prow = threadIdx.x / C8, PPB = 256 / C8;      // C8 in {1,2,4,...,32} divides 256: every thread has a pixel row
+    const act_lane L = {c8 * (int)sizeof(T), c8, S.has_cm ? c8 * 4 : c8 * (int)sizeof(T)};
+    long pix = (long)blockIdx.x * PPB + prow;
+    const long step = (long)gridDim.x * PPB, last = npix - 1;
+    // ---- the per-channel constants and the first trip ----
+    // reduce: scale, shift, mean, invstd and the first trip together: one round trip (see cM below).  apply with bn == 1: mean, invstd, gamma and the 16 totals of the
+    // thread's channels (straight from row 0, written by act_bwd_sum_kernel together with dgamma / dbeta: no copy through LDS, no barrier) become
+    // k0, cB, cC first; scale, shift and the first trip follow together: two round trips -- all seven vectors and a trip in flight at once need
+    // more registers than the phase may use.  apply without it: scale, shift and the first trip, one round trip.
+    if (scale) { ld8g(scale + c8 * 4, sa); ld8g(shift + c8 * 4, sb); }
+    // reduce forms cM BEHIND the first trip's requests and a scheduling barrier: in front of them its wait for mean and invstd stood between the
+    // constants and the first trip (and the compiler then folded that request into the loop's: two round trips).  Except the general fp32 instance:
+    // mean, invstd and its 53-register trip in flight together take 130 VGPRs, 3 waves per SIMD; cM first keeps it at 121 and at two round trips.
+    constexpr bool CM_FIRST = GEN && sizeof(T) == 4;
+    float mean[8];
+    if (!APPLY) { ld8g(meanp + c8 * 4, mean); ld8g(istdp + c8 * 4, istd); }      // (the entry point checks bn != 0)
+    if (!APPLY && CM_FIRST) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const f32x2 d = {dz[2 * j], dz[2 * j + 1]}, r2 = {raw[2 * j], raw[2 * j + 1]};
-                    const f32x2 i2 = {istd[2 * j], istd[2 * j + 1]}, m2 = {cM[2 * j], cM[2 * j + 1]};
-                    const f32x2 xh = r2 * i2 + m2;
-                    f32x2 a = {s0[2 * j], s0[2 * j + 1]}, b = {s1[2 * j], s1[2 * j + 1]};
-                    a = a + d; b = d * xh + b;
-                    s0[2 * j] = a.x; s0[2 * j + 1] = a.y; s1[2 * j] = b.x; s1[2 * j + 1] = b.y;
-                }
-            } else {
-                float o[8];
-                actbwd_apply8(dz, raw, k0, cB, cC, o);         // bn != 1: cB = cC = 0 -> dz*k0
-                st8((T*)P.gout + pix * C + c8, o);
+        for (int j = 0; j < 8; ++j) cM[j] = -mean[j] * istd[j];      // xhat = raw*istd + cM
+    }
+    act_trip<T> cur;
+    act_issue<T, GEN>(S, L, (u32)(pix < last ? pix : last), cur);
+    if (!APPLY && !CM_FIRST) {
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) cM[j] = -mean[j] * istd[j];
+    }
+    if (APPLY && bn != 1 && scale) {                   // fixed affine (eval-mode BN): dz/draw = scale
+#pragma unroll
+        for (int j = 0; j < 8; ++j) k0[j] = sa[j];
+    }
+    for (; pix < npix; pix += step) {
+        float raw[8], dz[8], gsum[8];
+        act_gsum<T, GEN>(S, cur, gsum);
+        act_bwd_dz<T, GEN>(S, cur, gsum, sa, sb, raw, dz);
+        if (!APPLY) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const f32x2 d = {dz[2 * j], dz[2 * j + 1]}, r2 = {raw[2 * j], raw[2 * j + 1]};
+                const f32x2 i2 = {istd[2 * j], istd[2 * j + 1]}, m2 = {cM[2 * j], cM[2 * j + 1]};
+                const f32x2 xh = r2 * i2 + m2;
+                f32x2 a = {s0[2 * j], s0[2 * j + 1]}, b = {s1[2 * j], s1[2 * j + 1]};
+                a = a + d; b = d * xh + b;
+                s0[2 * j] = a.x; s0[2 * j + 1] = a.y; s1[2 * j] = b.x; s1[2 * j + 1] = b.y;
             }
+        } else {
+            float o[8];
+            actbwd_apply8(dz, raw, k0, cB, cC, o);         // bn != 1: cB = cC = 0 -> dz*k0
+            st8g(gout + pix * C + c8, o);
         }
+        // the next trip as soon as this one is consumed, into the same registers; past the end the last pixel again (in bounds, never used: one
+        // trip of cache-resident loads per thread.  A wave-uniform branch that skips it when no lane goes on costs 8 to 13 VGPRs in every
+        // instance -- one-gradient apply 80 -> 88, general reduce fp32 121 -> 134, 3 waves per SIMD -- and was not kept).
+        // (A second register set, requested one trip ahead, won 6 % stand-alone at 256^2 and nothing on the whole iteration: DESIGN.md section 5.)
+        const long pn = pix + step < last ? pix + step : last;
+        act_issue<T, GEN>(S, L, (u32)pn, cur);
     }
     if (!APPLY) {
         for (int i = threadIdx.x; i < 4 * 2 * C; i += 256) red[i] = 0.f;
@@ -689,10 +857,10 @@ __device__ __forceinline__ void act_bwd_kernel(const chap_act_bwd_params& P) {
             else if (C8 == 4) { a = row16_stride_sum<4>(a); b = row16_stride_sum<4>(b); }
             else if (C8 == 8) { a = row16_stride_sum<8>(a); b = row16_stride_sum<8>(b); }
             for (int o = (C8 > 16 ? C8 : 16); o < 64; o <<= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); }
-            if ((threadIdx.x & 63) < C8 && prow < PPB) { red[(wave * 2 + 0) * C + c8 + j] = a; red[(wave * 2 + 1) * C + c8 + j] = b; }
+            if ((threadIdx.x & 63) < C8) { red[(wave * 2 + 0) * C + c8 + j] = a; red[(wave * 2 + 1) * C + c8 + j] = b; }
         }
         __syncthreads();
-        float* dst = P.sums + (long)(1 + blockIdx.x) * 2 * C;
+        CHAP_GLOBAL float* dst = sums + (long)(1 + blockIdx.x) * 2 * C;
         for (int i = threadIdx.x; i < 2 * C; i += 256) {
             const int which = i / C, c = i % C;
             dst[i] = (red[(0 * 2 + which) * C + c] + red[(1 * 2 + which) * C + c]) + (red[(2 * 2 + which) * C + c] + red[(3 * 2 + which) * C + c]);
@@ -703,10 +871,17 @@ __device__ __forceinline__ void act_bwd_kernel(const chap_act_bwd_params& P) {
 // Fixed-order total of the per-block partial rows (one wave per value, fp64) into row 0, read by the apply phase;
 // accumulates the BatchNorm parameter gradients.
 struct act_bwd_sum_args { float* sums; int nblocks; float* dgamma; float* dbeta; int C; };
-__device__ __forceinline__ void act_bwd_sum_kernel(const act_bwd_sum_args& A) {
-    float* sums = A.sums; const int nblocks = A.nblocks; float* dgamma = A.dgamma; float* dbeta = A.dbeta; const int C = A.C;
+__device__ __forceinline__ void act_bwd_sum_kernel(const act_bwd_sum_args& Ak) {
+    const act_bwd_sum_args A = chap_args_once(Ak);          // one scalar load and wait instead of three
+    CHAP_GLOBAL float* const sums = (CHAP_GLOBAL float*)A.sums; const int nblocks = A.nblocks, C = A.C;
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (i >= 2 * C) return;
+    // the parameter gradient this total is added to is requested NOW, next to the partial rows: behind the reduction it was one more
+    // dependent memory round trip of a kernel that is nothing but latency
+    CHAP_GLOBAL float* const acc = (CHAP_GLOBAL float*)(i < C ? A.dbeta : A.dgamma);
+    const int ai = i < C ? i : i - C;
+    float prior = 0.f;
+    if (acc) prior = acc[ai];
     double t = 0.0;
     constexpr int NB = CHAP_ACT_BWD_SLOTS / 64;                  // all of a lane's loads in flight at once, adds in the fixed order
     float vv[NB];
@@ -721,13 +896,19 @@ __device__ __forceinline__ void act_bwd_sum_kernel(const act_bwd_sum_args& A) {
     if (lane != 0) return;
     const float v = (float)t;
     sums[i] = v;
-    if (i < C) { if (dbeta) dbeta[i] += v; } else if (dgamma) dgamma[i - C] += v;
+    if (acc) acc[ai] = prior + v;
 }
 
 static int act_bwd_check(const chap_act_bwd_params* p) {
     CHAP_CHECK_ARG(p && p->r.ptr, "chap_act_bwd: null argument");
     CHAP_CHECK_ARG(p->r.C % 8 == 0 && 256 % (p->r.C / 8) == 0 && p->r.C <= 1024, "chap_act_bwd: C=%d unsupported", p->r.C);
     CHAP_CHECK_ARG(p->ng >= 0 && p->ng <= 3, "chap_act_bwd: ng=%d", p->ng);
+    {   // the kernels address every tensor with a 32-bit byte offset from its base
+        long ld = p->r.ld > p->r.C ? p->r.ld : p->r.C;
+        for (int k = 0; k < p->ng; ++k) ld = p->g_ld[k] > ld ? p->g_ld[k] : ld;
+        const long bytes = (long)p->N * p->D * p->H * p->W * ld * (p->dtype == CHAP_BF16 ? 2 : 4);
+        CHAP_CHECK_ARG(bytes < (1l << 32), "chap_act_bwd: a tensor of %ld bytes (4 GB at most)", bytes);
+    }
     CHAP_CHECK_ARG(p->bn >= 0 && p->bn <= 2, "chap_act_bwd: bn=%d", p->bn);
     CHAP_CHECK_ARG(p->bn != 1 || (p->mean && p->invstd && p->gamma && p->sums), "chap_act_bwd: bn=1 needs mean/invstd/gamma/sums");
     CHAP_CHECK_ARG(!p->g_pool || (p->pool_idx && p->D == 1 && p->H % 2 == 0 && p->W % 2 == 0), "chap_act_bwd: pooled gradient needs idx and even 2D dims");
@@ -746,13 +927,22 @@ static int act_bwd_blocks(const chap_act_bwd_params* p) {
     if (cap > CHAP_ACT_BWD_SLOTS) cap = 512;
     return (int)(b < cap ? b : cap);          // one partial row per block
 }
+// The instance of a layer: GEN = false for exactly one incoming gradient, no pooled gradient, no channel multipliers.
+template <typename T, bool APPLY>
+static int act_bwd_launch_t(const chap_act_bwd_params* p, int nb, size_t lds, hipStream_t s, const char* name) {
+    if (p->ng == 1 && !p->g_pool && !p->r.chan_mul) return chap_launch<chap_act_bwd_params, act_bwd_kernel<T, APPLY, false>, 256>(dim3(nb), dim3(256), lds, s, *p, name);
+    return chap_launch<chap_act_bwd_params, act_bwd_kernel<T, APPLY, true>, 256>(dim3(nb), dim3(256), lds, s, *p, name);
+}
+template <bool APPLY>
+static int act_bwd_launch(const chap_act_bwd_params* p, int nb, size_t lds, hipStream_t s, const char* name) {
+    return p->dtype == CHAP_BF16 ? act_bwd_launch_t<bf16_t, APPLY>(p, nb, lds, s, name) : act_bwd_launch_t<float, APPLY>(p, nb, lds, s, name);
+}
 extern "C" int chap_act_bwd_reduce(const chap_act_bwd_params* p, void* stream) {
     int r = act_bwd_check(p); if (r) return r;
     CHAP_CHECK_ARG(p->bn && p->mean && p->invstd && p->sums, "chap_act_bwd_reduce: needs bn, mean, invstd, sums");
     const size_t lds = 4 * 2 * p->r.C * sizeof(float);
     const int nb = act_bwd_blocks(p);              // one partial row per block
-    if (p->dtype == CHAP_BF16) r = chap_launch<chap_act_bwd_params, act_bwd_kernel<bf16_t, false>, 256>(dim3(nb), dim3(256), lds, (hipStream_t)stream, *p, "chap_act_bwd_reduce");
-    else r = chap_launch<chap_act_bwd_params, act_bwd_kernel<float, false>, 256>(dim3(nb), dim3(256), lds, (hipStream_t)stream, *p, "chap_act_bwd_reduce");
+    r = act_bwd_launch<false>(p, nb, lds, (hipStream_t)stream, "chap_act_bwd_reduce");
     if (r) return r;
     if (chap_lab_skip(KNOB_LAB_SKIP_ACTSUM)) return CHAP_OK;      // lab builds only: timing bound, wrong numerics
     const act_bwd_sum_args sa = {p->sums, nb, p->dgamma, p->dbeta, p->r.C};
@@ -762,9 +952,7 @@ extern "C" int chap_act_bwd_apply(const chap_act_bwd_params* p, void* stream) {
     int r = act_bwd_check(p); if (r) return r;
     CHAP_CHECK_ARG(p->gout, "chap_act_bwd_apply: null gout");
     if (chap_lab_skip(KNOB_LAB_SKIP_ACTAPPLY) && p->bn == 1) return CHAP_OK;      // lab builds only: timing bound (wrong numerics) for folding this pass into the loads of its consumers
-    const size_t lds = 2 * p->r.C * sizeof(float);
-    if (p->dtype == CHAP_BF16) return chap_launch<chap_act_bwd_params, act_bwd_kernel<bf16_t, true>, 256>(dim3(act_bwd_blocks(p)), dim3(256), lds, (hipStream_t)stream, *p, "chap_act_bwd_apply");
-    return chap_launch<chap_act_bwd_params, act_bwd_kernel<float, true>, 256>(dim3(act_bwd_blocks(p)), dim3(256), lds, (hipStream_t)stream, *p, "chap_act_bwd_apply");
+    return act_bwd_launch<true>(p, act_bwd_blocks(p), 0, (hipStream_t)stream, "chap_act_bwd_apply");      // (no LDS: the totals come straight from row 0)
 }
 
 // =========================================================================================

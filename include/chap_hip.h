@@ -244,7 +244,9 @@ int chap_bn_eval_affine(const chap_bn_eval_params* p, void* stream);
  *   phase 2 (apply):  g = gamma*invstd*(dz - sums0/cnt - rhat*sums1/cnt)  -> gout (dtype)
  * Incoming gradients: up to 3 same-grid tensors (ptr, ld, coff) and one half-resolution pooled
  * gradient routed through the saved arg-max index. With bn == 0 (no BatchNorm after the conv)
- * phase 2 writes g = dz and no sums are needed. */
+ * phase 2 writes g = dz and no sums are needed.
+ * Every tensor is addressed with a 32-bit byte offset from its base: pixels x the widest pixel stride (r.ld, r.C, g_ld[k]) x the element
+ * size must stay below 4 GB, or both entry points return CHAP_EINVAL before any launch. */
 typedef struct {
     const void* g[3];  int32_t g_ld[3];  int32_t g_coff[3];  int32_t ng;
     const void* g_pool; const uint8_t* pool_idx;     /* [N][H/2][W/2][C] each, or NULL           */
