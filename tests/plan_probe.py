@@ -1,5 +1,5 @@
 """The host-only planner probe shared by the CPU tests that ask chap_conv_fwd / chap_wgrad for their launch plans (tests/test_launch_plan_cpu.py,
-tests/test_small_conv_cases_cpu.py): a small stand-alone program, built with the host compiler from chap_amd/csrc/conv_plan.h, wgrad_plan.h and
+tests/test_small_conv_cases_cpu.py, tests/test_k3_conv_cases_cpu.py): a small stand-alone program, built with the host compiler from chap_amd/csrc/conv_plan.h, wgrad_plan.h and
 error.cpp, that reads request lines and prints one plan per line.  A helper module, not a conftest."""
 import os
 import subprocess
@@ -80,7 +80,7 @@ int main() {
             memset(&q, 0, sizeof(q));
             const int rc = wg_make_plan(&p, &q);
             if (rc) printf("rc=%d error=%s\n", rc, chap_last_error());
-            else printf("rc=0 brick=%d KC=%d bn=%d mr=%d nsplit=%d Ca=%d Cb=%d taps=%d bytes=%zu\n", q.brick, q.KC, q.bn, q.mr, q.nsplit, q.Ca, q.Cb, q.taps, q.bytes);
+            else printf("rc=0 brick=%d KC=%d bn=%d mr=%d nsplit=%d Ca=%d Cb=%d taps=%d bytes=%zu ntiles=%ld\n", q.brick, q.KC, q.bn, q.mr, q.nsplit, q.Ca, q.Cb, q.taps, q.bytes, q.ntiles);
         } else if (op == "pack") {
             chap_pack_params p;
             memset(&p, 0, sizeof(p));
