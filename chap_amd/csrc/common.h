@@ -98,6 +98,46 @@ __device__ __forceinline__ void ld4(const bf16_t* p, float v[4]) {
     v[2] = __uint_as_float(a.y << 16); v[3] = __uint_as_float(a.y & 0xffff0000u);
 }
 
+// Index decoding uses 32-bit unsigned arithmetic (64-bit integer division costs ~100 VALU instructions on
+// gfx950 and turned these streaming kernels VALU-bound); entry points reject tensors with >= 2^32 elements.
+typedef unsigned int u32;
+
+// A kernel's argument block read ONCE, in front of everything else: every word is pinned to a scalar register here, so the compiler cannot
+// sink the scalar loads next to their uses (it does, and each group of them is then one more dependent wait in front of the first load).
+// Cost: the whole block sits in scalar registers at the top (50 to 60 of them: act_bwd 49-65 -> 74-84 SGPRs, bn_finalize 56 -> 70, of 102), so only for
+// kernels with room.  The argument structs have padding (after `ng` in chap_act_bwd_params): the bit cast copies those bytes as whatever the launch
+// put there, nothing reads them, and the cast back leaves them padding again; formally their value is indeterminate, which is why no
+// has_unique_object_representations assert can stand here.
+template <typename A>
+__device__ __forceinline__ A chap_args_once(const A& p) {
+    static_assert(sizeof(A) % 4 == 0, "argument block is not a whole number of words");
+    struct words { uint32_t w[sizeof(A) / 4]; };
+    words w = __builtin_bit_cast(words, p);
+#pragma unroll
+    for (unsigned i = 0; i < sizeof(A) / 4; ++i) asm volatile("" : "+s"(w.w[i]));
+    return __builtin_bit_cast(A, w);
+}
+// ... a pointer that went through a register pin is a generic one to the compiler (flat loads and stores: both wait counters): the kernel
+// says that it is global where it uses it
+#define CHAP_GLOBAL __attribute__((address_space(1)))
+typedef const CHAP_GLOBAL char* chap_gptr;
+typedef float f32x4n __attribute__((ext_vector_type(4)));         // native vectors: the HIP vector classes have no members for a qualified address space
+typedef uint32_t u32x4n __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2n __attribute__((ext_vector_type(2)));
+template <typename X> __device__ __forceinline__ chap_gptr chap_global(const X* p) { return (chap_gptr)p; }
+template <typename V> __device__ __forceinline__ V ldg(chap_gptr p) { return *(const CHAP_GLOBAL V*)p; }
+__device__ __forceinline__ void ld8g(chap_gptr p, float v[8]) {
+    const f32x4n a = ldg<f32x4n>(p), b = ldg<f32x4n>(p + 16);
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+}
+__device__ __forceinline__ void st8g(CHAP_GLOBAL float* p, const float v[8]) {
+    *(CHAP_GLOBAL f32x4n*)p = f32x4n{v[0], v[1], v[2], v[3]};
+    *(CHAP_GLOBAL f32x4n*)(p + 4) = f32x4n{v[4], v[5], v[6], v[7]};
+}
+__device__ __forceinline__ void st8g(CHAP_GLOBAL bf16_t* p, const float v[8]) {
+    *(CHAP_GLOBAL u32x4n*)p = u32x4n{pack2bf(v[0], v[1]), pack2bf(v[2], v[3]), pack2bf(v[4], v[5]), pack2bf(v[6], v[7])};
+}
+
 // Load 8 channels [c8, c8+8) of pixel `pix` (global pixel index, sample `n`) of a lazy activation.
 template <typename T>
 __device__ __forceinline__ void src_load8(const chap_src_t& s, int n, long pix, int c8, float v[8]) {

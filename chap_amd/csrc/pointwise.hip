@@ -8,51 +8,11 @@
 #include "actbwd_math.h"
 #include "conv_c1_mfma.h"
 
-// Index decoding uses 32-bit unsigned arithmetic (64-bit integer division costs ~100 VALU instructions on
-// gfx950 and turned these streaming kernels VALU-bound); entry points reject tensors with >= 2^32 elements.
-typedef unsigned int u32;
-
 // Fixed-order wave reduction in fp64 (xor butterfly: the same pairing on every run).
 __device__ __forceinline__ double wave_sum_f64(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
-}
-
-// A kernel's argument block read ONCE, in front of everything else: every word is pinned to a scalar register here, so the compiler cannot
-// sink the scalar loads next to their uses (it does, and each group of them is then one more dependent wait in front of the first load).
-// Cost: the whole block sits in scalar registers at the top (50 to 60 of them: act_bwd 49-65 -> 74-84 SGPRs, bn_finalize 56 -> 70, of 102), so only for
-// kernels with room.  The argument structs have padding (after `ng` in chap_act_bwd_params): the bit cast copies those bytes as whatever the launch
-// put there, nothing reads them, and the cast back leaves them padding again; formally their value is indeterminate, which is why no
-// has_unique_object_representations assert can stand here.
-template <typename A>
-__device__ __forceinline__ A chap_args_once(const A& p) {
-    static_assert(sizeof(A) % 4 == 0, "argument block is not a whole number of words");
-    struct words { uint32_t w[sizeof(A) / 4]; };
-    words w = __builtin_bit_cast(words, p);
-#pragma unroll
-    for (unsigned i = 0; i < sizeof(A) / 4; ++i) asm volatile("" : "+s"(w.w[i]));
-    return __builtin_bit_cast(A, w);
-}
-// ... a pointer that went through a register pin is a generic one to the compiler (flat loads and stores: both wait counters): the kernel
-// says that it is global where it uses it
-#define CHAP_GLOBAL __attribute__((address_space(1)))
-typedef const CHAP_GLOBAL char* chap_gptr;
-typedef float f32x4n __attribute__((ext_vector_type(4)));         // native vectors: the HIP vector classes have no members for a qualified address space
-typedef uint32_t u32x4n __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2n __attribute__((ext_vector_type(2)));
-template <typename X> __device__ __forceinline__ chap_gptr chap_global(const X* p) { return (chap_gptr)p; }
-template <typename V> __device__ __forceinline__ V ldg(chap_gptr p) { return *(const CHAP_GLOBAL V*)p; }
-__device__ __forceinline__ void ld8g(chap_gptr p, float v[8]) {
-    const f32x4n a = ldg<f32x4n>(p), b = ldg<f32x4n>(p + 16);
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
-__device__ __forceinline__ void st8g(CHAP_GLOBAL float* p, const float v[8]) {
-    *(CHAP_GLOBAL f32x4n*)p = f32x4n{v[0], v[1], v[2], v[3]};
-    *(CHAP_GLOBAL f32x4n*)(p + 4) = f32x4n{v[4], v[5], v[6], v[7]};
-}
-__device__ __forceinline__ void st8g(CHAP_GLOBAL bf16_t* p, const float v[8]) {
-    *(CHAP_GLOBAL u32x4n*)p = u32x4n{pack2bf(v[0], v[1]), pack2bf(v[2], v[3]), pack2bf(v[4], v[5]), pack2bf(v[6], v[7])};
 }
 
 // =========================================================================================
@@ -361,7 +321,135 @@ extern "C" int chap_bn_eval_affine(const chap_bn_eval_params* p, void* stream) {
 }
 
 // =========================================================================================
+// A lazy source (chap_src_t) as the streaming kernels below ask for it: src_load8 (common.h) with its loads taken out of its branches.
+// src_load8 loads the raw values, then -- each behind a branch on a pointer of the argument block -- scale and shift, the keep mask and
+// the channel multipliers: up to three dependent memory round trips per pixel, and a kernel that walks several pixels per output
+// (a pool window, the corners of an up-sampling cell) in a loop pays them once per pixel.  Here, as in act_issue below:
+//  * the argument block is read once (chap_args_once) into a wave-uniform src_plan: byte base and byte stride of every part, presence;
+//  * src_issue requests the keep mask and the raw values of one pixel, src_issue_cm the multipliers of one sample, with no branch between
+//    the requests: a part the source does not have points at the 16 bytes of the pixel's own raw load -- a valid address whose line is
+//    requested anyway -- and its value is never used.  A kernel requests ALL pixels of an output before it uses the first;
+//  * src_finish applies affine -> LeakyReLU -> keep -> multipliers with src_load8's operations in src_load8's order: the same bits;
+//  * scale and shift are requested once per thread, in front of the loop, where the thread's channel group is the same on every trip
+//    (FIXC: gridDim.x * 256 a multiple of C / 8), and by src_issue_aff with the trip's loads otherwise;
+//  * KM = false is the source without keep mask and multipliers: it requests raw only;
+//  * A32: byte offsets are 32-bit, added to a scalar base, where the entry point saw every tensor below 4 GB; 64-bit otherwise.
+// Who uses it: channel_sum_kernel, every instance; the 2D pool and the up-sampling cell kernel for KM = false and A32 = true (the "plain" kernels) --
+// with a keep mask or multipliers in flight for 4 / 8 pixels they need more registers than the waves per SIMD of the general kernels allow
+// (DESIGN.md section 5), so those sources, and tensors of 4 GB and more, keep the general kernels on src_load8.
+template <typename T> struct act_pk;                        // 8 channels as loaded
+template <> struct act_pk<bf16_t> { u32x4n v; };
+template <> struct act_pk<float> { f32x4n a, b; };
+__device__ __forceinline__ void pk_ld(chap_gptr p, act_pk<bf16_t>& r) { r.v = ldg<u32x4n>(p); }
+__device__ __forceinline__ void pk_ld(chap_gptr p, act_pk<float>& r) { r.a = ldg<f32x4n>(p); r.b = ldg<f32x4n>(p + 16); }
+__device__ __forceinline__ void pk_unpack(const act_pk<bf16_t>& r, float v[8]) {      // the conversions of ld8 (common.h)
+    v[0] = __uint_as_float(r.v.x << 16); v[1] = __uint_as_float(r.v.x & 0xffff0000u);
+    v[2] = __uint_as_float(r.v.y << 16); v[3] = __uint_as_float(r.v.y & 0xffff0000u);
+    v[4] = __uint_as_float(r.v.z << 16); v[5] = __uint_as_float(r.v.z & 0xffff0000u);
+    v[6] = __uint_as_float(r.v.w << 16); v[7] = __uint_as_float(r.v.w & 0xffff0000u);
+}
+__device__ __forceinline__ void pk_unpack(const act_pk<float>& r, float v[8]) {
+    v[0] = r.a.x; v[1] = r.a.y; v[2] = r.a.z; v[3] = r.a.w; v[4] = r.b.x; v[5] = r.b.y; v[6] = r.b.z; v[7] = r.b.w;
+}
+
+template <bool A32> struct src_off { typedef u32 t; };
+template <> struct src_off<false> { typedef unsigned long t; };
+// wave-uniform: lives in scalar registers.  Element i of a part sits at base + i * stride + (the lane's channel offset), in bytes
+struct src_plan {
+    chap_gptr raw, keep, cm, scale, shift;
+    u32 raw_stride, keep_stride, cm_stride;                 // per pixel (raw, keep mask), per sample (multipliers); an absent part has raw's
+    bool has_aff, act, has_keep, has_cm;
+    int cm_hi, aff_hi;                                      // byte offset of channels 4..7 of the multipliers / of scale and shift (0 where they alias the raw load)
+    float slope, keep_scale;
+};
+template <typename T>
+__device__ __forceinline__ src_plan src_make_plan(const chap_src_t& r) {
+    constexpr u32 ES = sizeof(T);
+    src_plan S;
+    const u32 C = (u32)r.C;
+    S.raw = chap_global(r.ptr) + (long)r.coff * ES; S.raw_stride = (u32)r.ld * ES;
+    S.has_aff = r.scale != nullptr; S.act = r.act != 0; S.has_keep = r.keep != nullptr; S.has_cm = r.chan_mul != nullptr;
+    S.scale = chap_global(r.scale); S.shift = chap_global(r.shift);
+    S.keep = S.has_keep ? chap_global(r.keep) : S.raw; S.keep_stride = S.has_keep ? C : S.raw_stride;
+    S.cm = S.has_cm ? chap_global(r.chan_mul) : S.raw; S.cm_stride = S.has_cm ? C * 4 : S.raw_stride;
+    S.cm_hi = S.has_cm ? 16 : 0; S.aff_hi = S.has_aff ? 16 : 0;
+    S.slope = r.slope; S.keep_scale = r.keep_scale;
+    return S;
+}
+// the lane's channel offset in bytes: of the element type (raw), of the byte mask (an absent mask reads the first 8 bytes of the lane's own
+// raw unit or of an earlier one of the same pixel: c8 <= c8 * sizeof(T)), of the multipliers, of scale and shift
+struct src_lane { int t, b, cm, c4; };
+template <typename T>
+__device__ __forceinline__ src_lane src_make_lane(const src_plan& S, int c8) { return {c8 * (int)sizeof(T), c8, S.has_cm ? c8 * 4 : c8 * (int)sizeof(T), c8 * 4}; }
+
+template <typename T> struct src_trip { act_pk<T> raw; u32x2n keep; };       // one pixel as loaded
+struct src_vec8 { f32x4n lo, hi; };                                          // 8 floats as loaded: multipliers, scale, shift
+__device__ __forceinline__ void vec8_unpack(const src_vec8& m, float v[8]) { v[0] = m.lo.x; v[1] = m.lo.y; v[2] = m.lo.z; v[3] = m.lo.w; v[4] = m.hi.x; v[5] = m.hi.y; v[6] = m.hi.z; v[7] = m.hi.w; }
+
+template <bool A32>
+__device__ __forceinline__ chap_gptr src_addr(chap_gptr base, u32 stride, typename src_off<A32>::t i, int lane) {
+    typedef typename src_off<A32>::t OFF;
+    return base + (OFF)(i * (OFF)stride + (OFF)lane);       // A32: scalar base + 32-bit lane offset, no 64-bit address kept or computed per lane
+}
+// keep mask and raw values of pixel `pix`.  The raw load goes LAST: loads return in order, so the wait in front of a pixel's first use covers the pixel
+template <typename T, bool KM, bool A32>
+__device__ __forceinline__ void src_issue(const src_plan& S, const src_lane& L, typename src_off<A32>::t pix, src_trip<T>& t) {
+    if (KM) t.keep = ldg<u32x2n>(src_addr<A32>(S.keep, S.keep_stride, pix, L.b));
+    pk_ld(src_addr<A32>(S.raw, S.raw_stride, pix, L.t), t.raw);
+}
+// the multipliers of sample `n`; `pix`: any pixel the caller requests on this trip (what an absent part aliases)
+template <bool KM, bool A32>
+__device__ __forceinline__ void src_issue_cm(const src_plan& S, const src_lane& L, int n, typename src_off<A32>::t pix, src_vec8& m) {
+    typedef typename src_off<A32>::t OFF;
+    if (!KM) return;
+    const chap_gptr cp = src_addr<A32>(S.cm, S.cm_stride, S.has_cm ? (OFF)n : pix, L.cm);
+    m.lo = ldg<f32x4n>(cp); m.hi = ldg<f32x4n>(cp + S.cm_hi);
+}
+// scale and shift of the lane's channels with a trip's loads (the kernels whose threads change their channel group between trips)
+template <bool A32>
+__device__ __forceinline__ void src_issue_aff(const src_plan& S, const src_lane& L, typename src_off<A32>::t pix, src_vec8& a, src_vec8& b) {
+    const chap_gptr rp = src_addr<A32>(S.raw, S.raw_stride, pix, L.t);
+    const chap_gptr ap = S.has_aff ? S.scale + L.c4 : rp, bp = S.has_aff ? S.shift + L.c4 : rp;
+    a.lo = ldg<f32x4n>(ap); a.hi = ldg<f32x4n>(ap + S.aff_hi); b.lo = ldg<f32x4n>(bp); b.hi = ldg<f32x4n>(bp + S.aff_hi);
+}
+// ... in front of the loop (one wave-uniform branch, once per thread)
+__device__ __forceinline__ void src_load_aff(const src_plan& S, const src_lane& L, float sa[8], float sb[8]) {
+    if (S.has_aff) { ld8g(S.scale + L.c4, sa); ld8g(S.shift + L.c4, sb); }
+}
+// src_load8's arithmetic on a loaded pixel: v = cm * keep * keep_scale * leaky(scale * raw + shift), every step where the source has it
+template <typename T, bool KM>
+__device__ __forceinline__ void src_finish(const src_plan& S, const src_trip<T>& t, const src_vec8& m, const float sa[8], const float sb[8], float v[8]) {
+    pk_unpack(t.raw, v);
+    if (S.has_aff) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = fmaf(v[j], sa[j], sb[j]);
+    }
+    if (S.act) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = v[j] > 0.f ? v[j] : v[j] * S.slope;
+    }
+    if (KM && S.has_keep) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const uint32_t w = j < 4 ? t.keep.x : t.keep.y;
+            v[j] = ((w >> (8 * (j & 3))) & 0xff) ? v[j] * S.keep_scale : 0.f;
+        }
+    }
+    if (KM && S.has_cm) {
+        float a[8];
+        vec8_unpack(m, a);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] *= a[j];
+    }
+}
+// what an entry point needs to pick the instance: KM = the source has a keep mask or multipliers
+static inline bool src_has_km(const chap_src_t& r) { return r.keep != nullptr || r.chan_mul != nullptr; }
+// ... and whether `pixels` pixels of a tensor with pixel stride `ld` elements stay below the 4 GB that 32-bit byte offsets reach
+static inline bool src_fits32(long pixels, long ld, int dtype) { return pixels * ld * (dtype == CHAP_BF16 ? 2 : 4) < (1l << 32); }
+
+// =========================================================================================
 // 2x2 max-pool of a lazy activation. One thread per (pooled pixel, 8 channels).
+// The general form: any source, any size, one sample of the window at a time through src_load8.
 template <typename T>
 __device__ __forceinline__ void act_pool2_kernel(const chap_pool_params& P) {
     const int D = P.D > 1 ? P.D : 1, KZ = P.D > 1 ? 2 : 1;
@@ -392,14 +480,71 @@ __device__ __forceinline__ void act_pool2_kernel(const chap_pool_params& P) {
         }
     }
 }
+// The 2D pool of a plain source (neither keep mask nor channel multipliers) below 4 GB -- every pool of the 2D training step.
+// All 4 samples of the window are requested together, then compared in the window's order k = 0, 1, 2, 3: the first maximum wins, a NaN replaces.
+// (Not the 3D window: 8 samples in flight take 122 to 126 registers, and one z plane at a time still more than the 80 of the 6 waves per SIMD the
+// general form runs at; nor keep mask / multipliers: 85 to 96.)
+template <typename T, bool FIXC>
+__device__ __forceinline__ void act_pool2_plain_body(const chap_pool_params& P, const src_plan& S) {
+    constexpr int ES = sizeof(T);
+    const int C = P.r.C, C8 = C / 8, OH = P.H / 2, OW = P.W / 2, W = P.W;
+    const long total = (long)P.N * OH * OW * C8;
+    CHAP_GLOBAL char* const out = (CHAP_GLOBAL char*)P.out; CHAP_GLOBAL char* const idx = (CHAP_GLOBAL char*)P.idx;
+    long i = (long)blockIdx.x * 256 + threadIdx.x;
+    float sa[8], sb[8];
+    if (FIXC) src_load_aff(S, src_make_lane<T>(S, (int)((u32)i % (u32)C8) * 8), sa, sb);
+    for (; i < total; i += (long)gridDim.x * 256) {
+        const u32 ui = (u32)i;
+        const int c8 = (int)(ui % (u32)C8) * 8; u32 r = ui / (u32)C8;
+        const u32 ox = r % (u32)OW; r /= (u32)OW;      // r: n * OH + oy, and H = 2 * OH
+        const src_lane L = src_make_lane<T>(S, c8);
+        const u32 p0 = (2 * r) * (u32)W + 2 * ox;      // sample k = 0 of the window
+        src_trip<T> w[4]; src_vec8 m, fa, fb;
+        if (!FIXC) src_issue_aff<true>(S, L, p0, fa, fb);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) src_issue<T, false, true>(S, L, p0 + (u32)((k >> 1) * W + (k & 1)), w[k]);
+        if (!FIXC) { vec8_unpack(fa, sa); vec8_unpack(fb, sb); }
+        float best[8]; uint32_t bi[8];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float v[8];
+            src_finish<T, false>(S, w[k], m, sa, sb, v);
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if (k == 0 || v[j] > best[j] || v[j] != v[j]) { best[j] = v[j]; bi[j] = k; }
+        }
+        const u32 op = r * (u32)OW + ox;
+        st8g((CHAP_GLOBAL T*)(out + (u32)((op * C + c8) * ES)), best);
+        if (idx) {
+            u32x2n mm;
+            mm.x = bi[0] | (bi[1] << 8) | (bi[2] << 16) | (bi[3] << 24);
+            mm.y = bi[4] | (bi[5] << 8) | (bi[6] << 16) | (bi[7] << 24);
+            *(CHAP_GLOBAL u32x2n*)(idx + (u32)(op * C + c8)) = mm;
+        }
+    }
+}
+template <typename T>
+__device__ __forceinline__ void act_pool2_plain_kernel(const chap_pool_params& Pk) {
+    const chap_pool_params P = chap_args_once(Pk);
+    const src_plan S = src_make_plan<T>(P.r);
+    if ((gridDim.x * 256u) % (u32)(P.r.C / 8) == 0) act_pool2_plain_body<T, true>(P, S);       // (wave-uniform)
+    else act_pool2_plain_body<T, false>(P, S);
+}
+template <typename T>
+static int act_pool2_launch(const chap_pool_params* p, bool plain, int blocks, hipStream_t s) {
+    const dim3 g(blocks), b(256);
+    if (plain) return chap_launch<chap_pool_params, act_pool2_plain_kernel<T>, 256, 6>(g, b, 0, s, *p, "chap_act_pool2");      // (6 waves per SIMD: as the general form)
+    return chap_launch<chap_pool_params, act_pool2_kernel<T>, 256>(g, b, 0, s, *p, "chap_act_pool2");
+}
 extern "C" int chap_act_pool2(const chap_pool_params* p, void* stream) {
     CHAP_CHECK_ARG(p && p->r.ptr && p->out, "chap_act_pool2: null argument");
     CHAP_CHECK_ARG(p->r.C % 8 == 0 && p->H % 2 == 0 && p->W % 2 == 0 && (p->D <= 1 || p->D % 2 == 0), "chap_act_pool2: C%%8, even dims required");
     if (chap_lab_skip(KNOB_LAB_SKIP_POOL)) return CHAP_OK;      // lab builds only: timing bound (wrong numerics) of fusing this launch into its consumer
     const long total = (long)p->N * (p->D > 1 ? p->D / 2 : 1) * (p->H / 2) * (p->W / 2) * (p->r.C / 8);
     const int blocks = chap_blocks(total, 4096);
-    if (p->dtype == CHAP_BF16) return chap_launch<chap_pool_params, act_pool2_kernel<bf16_t>, 256>(dim3(blocks), dim3(256), 0, (hipStream_t)stream, *p, "chap_act_pool2");
-    return chap_launch<chap_pool_params, act_pool2_kernel<float>, 256>(dim3(blocks), dim3(256), 0, (hipStream_t)stream, *p, "chap_act_pool2");
+    const bool plain = p->D <= 1 && !src_has_km(p->r) && src_fits32((long)p->N * p->H * p->W, p->r.ld > p->r.C ? p->r.ld : p->r.C, p->dtype);      // (the pooled output is smaller)
+    if (p->dtype == CHAP_BF16) return act_pool2_launch<bf16_t>(p, plain, blocks, (hipStream_t)stream);
+    return act_pool2_launch<float>(p, plain, blocks, (hipStream_t)stream);
 }
 
 // =========================================================================================
@@ -463,6 +608,7 @@ __device__ __forceinline__ int up_axis_outputs(int i, int in, int out, bool hp, 
     }
     return n;
 }
+// The general form: any source, any size, the corners one after the other through src_load8.
 template <typename T, bool D3>
 __device__ __forceinline__ void upsample2x_cell_kernel(const chap_upsample_params& P) {
     const int C8 = P.r.C / 8;
@@ -511,6 +657,89 @@ __device__ __forceinline__ void upsample2x_cell_kernel(const chap_upsample_param
                 }
     }
 }
+// The plain source (neither keep mask nor channel multipliers) below 4 GB.
+// The 4 / 8 corners are requested together (src_issue), then transformed (src_finish): one memory round trip per cell.
+template <typename T, bool KM, bool A32, bool D3, bool FIXC>
+__device__ __forceinline__ void upsample2x_cell_plain_body(const chap_upsample_params& P, const src_plan& S) {
+    typedef typename src_off<A32>::t OFF;
+    constexpr int NZ = D3 ? 2 : 1, ES = sizeof(T);
+    const int C8 = P.r.C / 8, D = P.D, H = P.H, W = P.W;
+    const int OD = D3 ? 2 * D : D, OH = 2 * H, OW = 2 * W;
+    const int CD = D3 ? D - 1 : D, CH = H - 1, CW = W - 1;       // cells per axis
+    const long total = (long)P.N * CD * CH * CW * C8;
+    const bool hp = P.half_pixel != 0;
+    CHAP_GLOBAL char* const out = (CHAP_GLOBAL char*)P.out + (long)P.out_coff * ES;
+    const OFF out_ld = (OFF)P.out_ld;
+    long i = (long)blockIdx.x * 256 + threadIdx.x;
+    float sa[8], sb[8];
+    if (FIXC) src_load_aff(S, src_make_lane<T>(S, (int)((u32)i % (u32)C8) * 8), sa, sb);
+    for (; i < total; i += (long)gridDim.x * 256) {
+        const u32 ui = (u32)i;
+        const int c8 = (int)(ui % (u32)C8) * 8; u32 r = ui / (u32)C8;
+        const int cx = (int)(r % (u32)CW); r /= (u32)CW;
+        const int cy = (int)(r % (u32)CH); r /= (u32)CH;
+        const int cz = (int)(r % (u32)CD); const int n = (int)(r / (u32)CD);
+        const src_lane L = src_make_lane<T>(S, c8);
+        const OFF p0 = (((OFF)n * D + cz) * H + cy) * W + cx;             // corner (0, 0, 0) of the cell
+        src_trip<T> t[NZ][2][2]; src_vec8 m, fa, fb;
+        if (!FIXC) src_issue_aff<A32>(S, L, p0, fa, fb);
+        src_issue_cm<KM, A32>(S, L, n, p0, m);
+#pragma unroll
+        for (int kz = 0; kz < NZ; ++kz)
+#pragma unroll
+            for (int ky = 0; ky < 2; ++ky)
+#pragma unroll
+                for (int kx = 0; kx < 2; ++kx) src_issue<T, KM, A32>(S, L, p0 + (OFF)((kz * H + ky) * W + kx), t[kz][ky][kx]);
+        if (!FIXC) { vec8_unpack(fa, sa); vec8_unpack(fb, sb); }
+        float v[NZ][2][2][8];
+#pragma unroll
+        for (int kz = 0; kz < NZ; ++kz)
+#pragma unroll
+            for (int ky = 0; ky < 2; ++ky)
+#pragma unroll
+                for (int kx = 0; kx < 2; ++kx) src_finish<T, KM>(S, t[kz][ky][kx], m, sa, sb, v[kz][ky][kx]);
+        int oz_[5], oy_[5], ox_[5]; float wz_[5], wy_[5], wx_[5];
+        int nz = 1; oz_[0] = cz; wz_[0] = 0.f;
+        if (D3) nz = up_axis_outputs(cz, D, OD, hp, oz_, wz_);
+        const int ny = up_axis_outputs(cy, H, OH, hp, oy_, wy_);
+        const int nx = up_axis_outputs(cx, W, OW, hp, ox_, wx_);
+        for (int a = 0; a < nz; ++a)
+            for (int b = 0; b < ny; ++b)
+                for (int c = 0; c < nx; ++c) {
+                    const float wz = wz_[a], wy = wy_[b], wx = wx_[c];
+                    float acc[8];
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+#pragma unroll
+                    for (int kz = 0; kz < NZ; ++kz)
+#pragma unroll
+                        for (int ky = 0; ky < 2; ++ky)
+#pragma unroll
+                            for (int kx = 0; kx < 2; ++kx) {
+                                const float w = (kz ? wz : 1.f - wz) * (ky ? wy : 1.f - wy) * (kx ? wx : 1.f - wx);
+#pragma unroll
+                                for (int j = 0; j < 8; ++j) acc[j] = fmaf(w, v[kz][ky][kx][j], acc[j]);
+                            }
+                    const OFF op = (((OFF)n * OD + oz_[a]) * OH + oy_[b]) * OW + ox_[c];
+                    st8g((CHAP_GLOBAL T*)(out + (OFF)((op * out_ld + c8) * ES)), acc);
+                }
+    }
+}
+template <typename T, bool KM, bool A32, bool D3>
+__device__ __forceinline__ void upsample2x_cell_plain_kernel(const chap_upsample_params& Pk) {
+    const chap_upsample_params P = chap_args_once(Pk);
+    const src_plan S = src_make_plan<T>(P.r);
+    if ((gridDim.x * 256u) % (u32)(P.r.C / 8) == 0) upsample2x_cell_plain_body<T, KM, A32, D3, true>(P, S);      // (wave-uniform)
+    else upsample2x_cell_plain_body<T, KM, A32, D3, false>(P, S);
+}
+// (5 waves per SIMD in 2D, 3 in 3D: what the kernel ran at before the corners were in flight together)
+template <typename T, bool D3>
+static int upsample2x_cell_launch(const chap_upsample_params* p, bool a32, int blocks, hipStream_t s) {
+    const dim3 g(blocks), b(256);
+    // (with a keep mask or multipliers in flight per corner: 100 to 108 registers in 2D, 4 waves per SIMD, or scratch: the general form)
+    if (!a32 || src_has_km(p->r)) return chap_launch<chap_upsample_params, upsample2x_cell_kernel<T, D3>, 256>(g, b, 0, s, *p, "chap_upsample2x");
+    return chap_launch<chap_upsample_params, upsample2x_cell_plain_kernel<T, false, true, D3>, 256, D3 ? 3 : 5>(g, b, 0, s, *p, "chap_upsample2x");
+}
 extern "C" int chap_upsample2x(const chap_upsample_params* p, void* stream) {
     CHAP_CHECK_ARG(p && p->r.ptr && p->out && p->r.C % 8 == 0, "chap_upsample2x: bad argument");
     CHAP_CHECK_ARG(p->out_ld % 8 == 0 && p->out_coff % 8 == 0, "chap_upsample2x: out_ld/out_coff must be multiples of 8");
@@ -520,16 +749,17 @@ extern "C" int chap_upsample2x(const chap_upsample_params* p, void* stream) {
         const long cells = (long)p->N * (d3 ? p->D - 1 : p->D) * (p->H - 1) * (p->W - 1) * (p->r.C / 8);
         const int blocks = chap_blocks(cells, 16384);
         hipStream_t s = (hipStream_t)stream;
-        if (p->dtype == CHAP_BF16) return d3 ? chap_launch<chap_upsample_params, upsample2x_cell_kernel<bf16_t, true>, 256>(dim3(blocks), dim3(256), 0, s, *p, "chap_upsample2x")
-                                             : chap_launch<chap_upsample_params, upsample2x_cell_kernel<bf16_t, false>, 256>(dim3(blocks), dim3(256), 0, s, *p, "chap_upsample2x");
-        return d3 ? chap_launch<chap_upsample_params, upsample2x_cell_kernel<float, true>, 256>(dim3(blocks), dim3(256), 0, s, *p, "chap_upsample2x")
-                  : chap_launch<chap_upsample_params, upsample2x_cell_kernel<float, false>, 256>(dim3(blocks), dim3(256), 0, s, *p, "chap_upsample2x");
+        const long ipix = (long)p->N * p->D * p->H * p->W;
+        const bool a32 = src_fits32(ipix, p->r.ld > p->r.C ? p->r.ld : p->r.C, p->dtype) && src_fits32(ipix * (d3 ? 8 : 4), p->out_ld, p->dtype);
+        if (p->dtype == CHAP_BF16) return d3 ? upsample2x_cell_launch<bf16_t, true>(p, a32, blocks, s) : upsample2x_cell_launch<bf16_t, false>(p, a32, blocks, s);
+        return d3 ? upsample2x_cell_launch<float, true>(p, a32, blocks, s) : upsample2x_cell_launch<float, false>(p, a32, blocks, s);
     }
     const long total = (long)p->N * (p->dims == 3 ? 2 * p->D : p->D) * 2 * p->H * 2 * p->W * (p->r.C / 8);
     const int blocks = chap_blocks(total, 8192);
     if (p->dtype == CHAP_BF16) return chap_launch<chap_upsample_params, upsample2x_kernel<bf16_t>, 256>(dim3(blocks), dim3(256), 0, (hipStream_t)stream, *p, "chap_upsample2x");
     return chap_launch<chap_upsample_params, upsample2x_kernel<float>, 256>(dim3(blocks), dim3(256), 0, (hipStream_t)stream, *p, "chap_upsample2x");
 }
+
 
 // Adjoint: each coarse pixel gathers from the fine pixels whose stencil touches it (no atomics).
 // Along one axis, fine index o touches coarse i iff i0(o) == i or i1(o) == i; with scale
@@ -626,21 +856,6 @@ extern "C" int chap_upsample2x_bwd(const chap_upsample_bwd_params* p, void* stre
 //  * reduce: the per-channel constants and the first trip go out together, one memory round trip in front of the loop (the general fp32
 //    instance: two).  apply: two (see the prologue of act_bwd_kernel for both).
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-template <typename T> struct act_pk;                        // 8 channels as loaded
-template <> struct act_pk<bf16_t> { u32x4n v; };
-template <> struct act_pk<float> { f32x4n a, b; };
-__device__ __forceinline__ void pk_ld(chap_gptr p, act_pk<bf16_t>& r) { r.v = ldg<u32x4n>(p); }
-__device__ __forceinline__ void pk_ld(chap_gptr p, act_pk<float>& r) { r.a = ldg<f32x4n>(p); r.b = ldg<f32x4n>(p + 16); }
-__device__ __forceinline__ void pk_unpack(const act_pk<bf16_t>& r, float v[8]) {      // the conversions of ld8 (common.h)
-    v[0] = __uint_as_float(r.v.x << 16); v[1] = __uint_as_float(r.v.x & 0xffff0000u);
-    v[2] = __uint_as_float(r.v.y << 16); v[3] = __uint_as_float(r.v.y & 0xffff0000u);
-    v[4] = __uint_as_float(r.v.z << 16); v[5] = __uint_as_float(r.v.z & 0xffff0000u);
-    v[6] = __uint_as_float(r.v.w << 16); v[7] = __uint_as_float(r.v.w & 0xffff0000u);
-}
-__device__ __forceinline__ void pk_unpack(const act_pk<float>& r, float v[8]) {
-    v[0] = r.a.x; v[1] = r.a.y; v[2] = r.a.z; v[3] = r.a.w; v[4] = r.b.x; v[5] = r.b.y; v[6] = r.b.z; v[7] = r.b.w;
-}
 
 struct act_src1 { chap_gptr base; u32 stride; };         // bytes; element i of the source sits at base + i * stride + (the lane's channel offset), all of it below 2^32
 // wave-uniform: lives in scalar registers
@@ -1021,19 +1236,39 @@ extern "C" int chap_cl_to_planar(const chap_cl_to_planar_params* p, void* stream
 // =========================================================================================
 // out[c] += sum over pixels of a (lazy) channel-last tensor: bias gradient of layers whose output
 // gradient is not the B operand of chap_wgrad (transposed conv).
-template <typename T>
-__device__ __forceinline__ void channel_sum_kernel(const chap_chansum_params& P) {
+// A thread's channel group never changes: scale and shift once, in front of the loop; a trip's loads through src_issue / src_issue_cm, the
+// next trip requested as soon as the current one is consumed (past the end: the last pixel again, in bounds, never used), as act_bwd_kernel.
+template <typename T, bool KM, bool A32>
+__device__ __forceinline__ void channel_sum_kernel(const chap_chansum_params& Pk) {
+    typedef typename src_off<A32>::t OFF;
     extern __shared__ float red[];             // [4 waves][C]
+    const chap_chansum_params P = chap_args_once(Pk);
+    const src_plan S = src_make_plan<T>(P.r);
     const int C = P.r.C, C8 = C / 8;
     const int c8 = (threadIdx.x % C8) * 8, prow = threadIdx.x / C8, PPB = 256 / C8;
-    float s[8];
+    const long npix = P.npix, last = npix > 0 ? npix - 1 : 0, step = (long)gridDim.x * PPB;
+    const u32 pps = (u32)P.pix_per_sample;
+    CHAP_GLOBAL float* const ws = (CHAP_GLOBAL float*)P.ws;
+    const src_lane L = src_make_lane<T>(S, c8);
+    float s[8], sa[8], sb[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) s[j] = 0.f;
-    for (long pix = (long)blockIdx.x * PPB + prow; pix < P.npix; pix += (long)gridDim.x * PPB) {
+    src_load_aff(S, L, sa, sb);
+    long pix = (long)blockIdx.x * PPB + prow;
+    src_trip<T> cur; src_vec8 m;
+    {
+        const long pc = pix < last ? pix : last;
+        src_issue_cm<KM, A32>(S, L, (int)((u32)pc / pps), (OFF)pc, m);
+        src_issue<T, KM, A32>(S, L, (OFF)pc, cur);
+    }
+    for (; pix < npix; pix += step) {
         float v[8];
-        src_load8<T>(P.r, (int)((u32)pix / (u32)P.pix_per_sample), pix, c8, v);
+        src_finish<T, KM>(S, cur, m, sa, sb, v);
 #pragma unroll
         for (int j = 0; j < 8; ++j) s[j] += v[j];
+        const long pn = pix + step < last ? pix + step : last;
+        src_issue_cm<KM, A32>(S, L, (int)((u32)pn / pps), (OFF)pn, m);
+        src_issue<T, KM, A32>(S, L, (OFF)pn, cur);
     }
     for (int i = threadIdx.x; i < 4 * C; i += 256) red[i] = 0.f;
     __syncthreads();
@@ -1045,18 +1280,37 @@ __device__ __forceinline__ void channel_sum_kernel(const chap_chansum_params& P)
         if ((threadIdx.x & 63) < C8) red[wave * C + c8 + j] = a;
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < C; i += 256) P.ws[(long)blockIdx.x * C + i] = (red[i] + red[C + i]) + (red[2 * C + i] + red[3 * C + i]);
+    for (int i = threadIdx.x; i < C; i += 256) ws[(long)blockIdx.x * C + i] = (red[i] + red[C + i]) + (red[2 * C + i] + red[3 * C + i]);
 }
-// out[c] += fixed-order total of the block partials (one wave per channel, fp64)
+// out[c] += fixed-order total of the block partials (one wave per channel, fp64).  As act_bwd_sum_kernel: the arguments once, all of a lane's
+// partial rows in flight at once, the prior out[c] requested next to them; the adds in the fixed ascending order.
 struct chansum_final_args { const float* ws; int nblocks, C; float* out; };
-__device__ __forceinline__ void channel_sum_final_kernel(const chansum_final_args& A) {
-    const float* ws = A.ws; const int nblocks = A.nblocks, C = A.C; float* out = A.out;
+__device__ __forceinline__ void channel_sum_final_kernel(const chansum_final_args& Ak) {
+    const chansum_final_args A = chap_args_once(Ak);
+    const CHAP_GLOBAL float* const ws = (const CHAP_GLOBAL float*)A.ws; CHAP_GLOBAL float* const out = (CHAP_GLOBAL float*)A.out;
+    const int nblocks = A.nblocks, C = A.C;
     const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (c >= C) return;
+    const float prior = out[c];
+    constexpr int NB = CHAP_CHANSUM_SLOTS / 64;                  // (the entry point launches CHAP_CHANSUM_SLOTS blocks at most)
+    float vv[NB];
+#pragma unroll
+    for (int k = 0; k < NB; ++k) {
+        const int b = lane + 64 * k;
+        vv[k] = ws[(long)(b < nblocks ? b : 0) * C + c];
+    }
     double t = 0.0;
-    for (int b = lane; b < nblocks; b += 64) t += (double)ws[(long)b * C + c];
+#pragma unroll
+    for (int k = 0; k < NB; ++k) if (lane + 64 * k < nblocks) t += (double)vv[k];
     t = wave_sum_f64(t);
-    if (lane == 0) out[c] += (float)t;
+    if (lane == 0) out[c] = prior + (float)t;
+}
+template <typename T>
+static int channel_sum_launch(const chap_chansum_params* p, bool a32, int nb, size_t lds, hipStream_t s) {
+    const dim3 g(nb), b(256);
+    if (!a32) return chap_launch<chap_chansum_params, channel_sum_kernel<T, true, false>, 256>(g, b, lds, s, *p, "chap_channel_sum");
+    if (src_has_km(p->r)) return chap_launch<chap_chansum_params, channel_sum_kernel<T, true, true>, 256>(g, b, lds, s, *p, "chap_channel_sum");
+    return chap_launch<chap_chansum_params, channel_sum_kernel<T, false, true>, 256>(g, b, lds, s, *p, "chap_channel_sum");
 }
 extern "C" int chap_channel_sum(const chap_chansum_params* p, void* stream) {
     CHAP_CHECK_ARG(p && p->r.ptr && p->out && p->ws && p->r.C % 8 == 0 && 256 % (p->r.C / 8) == 0 && p->r.C <= 512, "chap_channel_sum: bad argument");
@@ -1064,9 +1318,10 @@ extern "C" int chap_channel_sum(const chap_chansum_params* p, void* stream) {
     long b = (p->npix + ppb - 1) / ppb;
     const int nb = (int)(b < CHAP_CHANSUM_SLOTS ? b : CHAP_CHANSUM_SLOTS);
     const size_t lds = 4 * p->r.C * sizeof(float);
+    const bool a32 = src_fits32(p->npix, p->r.ld > p->r.C ? p->r.ld : p->r.C, p->dtype);
     int r;
-    if (p->dtype == CHAP_BF16) r = chap_launch<chap_chansum_params, channel_sum_kernel<bf16_t>, 256>(dim3(nb), dim3(256), lds, (hipStream_t)stream, *p, "chap_channel_sum");
-    else r = chap_launch<chap_chansum_params, channel_sum_kernel<float>, 256>(dim3(nb), dim3(256), lds, (hipStream_t)stream, *p, "chap_channel_sum");
+    if (p->dtype == CHAP_BF16) r = channel_sum_launch<bf16_t>(p, a32, nb, lds, (hipStream_t)stream);
+    else r = channel_sum_launch<float>(p, a32, nb, lds, (hipStream_t)stream);
     if (r) return r;
     const chansum_final_args fa = {(const float*)p->ws, nb, p->r.C, p->out};
     return chap_launch<chansum_final_args, channel_sum_final_kernel, 256>(dim3(cdiv(p->r.C, 4)), dim3(256), 0, (hipStream_t)stream, fa, "chap_channel_sum(final)");

@@ -14,48 +14,60 @@ extern "C" size_t chap_wgrad_ws(const chap_wgrad_params* p) {
 // few-slab / large-weight layers, E4 = 8 (G = 32) when there are many slabs of a small weight.
 // Fixed summation order -> bitwise reproducible.  total % 4 == 0 (Cb is a multiple of 16).
 // Blocks [0, nb_dw) reduce dW, blocks [nb_dw, ...) reduce the bias-gradient partials the same way.
+// The kernel is nothing but latency, so (as act_bwd_sum_kernel, pointwise.hip): the arguments are read once; the element's (tap, kc, kn0) is
+// decoded and the four prior dw / db values its g == 0 thread adds to are requested IN FRONT of the slab loop, next to the first slabs, not
+// behind the barrier where they were one more dependent memory round trip.  A prior that is not to be written (kn >= kn_valid, kc >= kc_valid)
+// is requested at the first valid one's address -- in bounds, never used.
 struct wgrad_reduce_args { const float* ws; const float* ws_db; int nsplit, taps, Ca, Cb; float* dw; long s_tap, s_kc, s_kn; int kc_valid, kn_valid; float* db; int nb_dw; };
 template <int E4>
-__device__ __forceinline__ void wgrad_reduce_kernel(const wgrad_reduce_args& A) {
+__device__ __forceinline__ void wgrad_reduce_kernel(const wgrad_reduce_args& Ak) {
+    const wgrad_reduce_args A = chap_args_once(Ak);
     const int bid = (int)blockIdx.x;
-    const float* __restrict__ ws = A.ws; const float* __restrict__ ws_db = A.ws_db;
-    const int nsplit = A.nsplit, taps = A.taps, Ca = A.Ca, Cb = A.Cb, kc_valid = A.kc_valid, kn_valid = A.kn_valid, nb_dw = A.nb_dw;
-    float* dw = A.dw; float* db = A.db;
-    const long s_tap = A.s_tap, s_kc = A.s_kc, s_kn = A.s_kn;
+    const int nsplit = A.nsplit, Ca = A.Ca, Cb = A.Cb, kc_valid = A.kc_valid, kn_valid = A.kn_valid, nb_dw = A.nb_dw;
     constexpr int G = 256 / E4;
     __shared__ float4 red[G][E4];
     const int col = threadIdx.x % E4, g = threadIdx.x / E4;
     const bool is_db = bid >= nb_dw;                             // bias gradient: Cb values x nsplit partials, same scheme
-    const long total = is_db ? (long)Cb : (long)taps * Ca * Cb;
+    const long total = is_db ? (long)Cb : (long)A.taps * Ca * Cb;
     const long i = ((long)(is_db ? bid - nb_dw : bid) * E4 + col) * 4;
+    // where the total goes: 4 consecutive kn of one (tap, kc) (Cb % 4 == 0); 32-bit division unless the weight has 2^32 elements (wave-uniform)
+    int kn0, kc, tap;
+    if (total < (1l << 32)) {
+        const u32 ui = (u32)i, r = ui / (u32)Cb;
+        kn0 = (int)(ui % (u32)Cb); kc = (int)(r % (u32)Ca); tap = (int)(r / (u32)Ca);
+    } else {
+        const long r = i / Cb;
+        kn0 = (int)(i % Cb); kc = (int)(r % Ca); tap = (int)(r / Ca);
+    }
+    const bool writer = g == 0 && i < total && (is_db || kc < kc_valid) && kn0 < kn_valid;
+    CHAP_GLOBAL float* const o = is_db ? (CHAP_GLOBAL float*)A.db + kn0 : (CHAP_GLOBAL float*)A.dw + tap * A.s_tap + kc * A.s_kc + kn0 * A.s_kn;
+    const long s_o = is_db ? 1 : A.s_kn;
+    float prior[4] = {0.f, 0.f, 0.f, 0.f};
+    if (writer) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) prior[j] = o[(kn0 + j < kn_valid ? j : 0) * s_o];
+    }
     float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0, s2 = s0, s3 = s0;
     if (i < total) {
-        const float* src = (is_db ? ws_db : ws) + i;
+        const CHAP_GLOBAL float* src = (const CHAP_GLOBAL float*)(is_db ? A.ws_db : A.ws) + i;
+        typedef const CHAP_GLOBAL f32x4n* f4p;
         int k = g;
         for (; k + 3 * G < nsplit; k += 4 * G) {
-            const float4 a = *(const float4*)(src + (long)k * total), b = *(const float4*)(src + (long)(k + G) * total);
-            const float4 c = *(const float4*)(src + (long)(k + 2 * G) * total), d = *(const float4*)(src + (long)(k + 3 * G) * total);
+            const f32x4n a = *(f4p)(src + (long)k * total), b = *(f4p)(src + (long)(k + G) * total);
+            const f32x4n c = *(f4p)(src + (long)(k + 2 * G) * total), d = *(f4p)(src + (long)(k + 3 * G) * total);
             s0.x += a.x; s0.y += a.y; s0.z += a.z; s0.w += a.w;  s1.x += b.x; s1.y += b.y; s1.z += b.z; s1.w += b.w;
             s2.x += c.x; s2.y += c.y; s2.z += c.z; s2.w += c.w;  s3.x += d.x; s3.y += d.y; s3.z += d.z; s3.w += d.w;
         }
-        for (; k < nsplit; k += G) { const float4 a = *(const float4*)(src + (long)k * total); s0.x += a.x; s0.y += a.y; s0.z += a.z; s0.w += a.w; }
+        for (; k < nsplit; k += G) { const f32x4n a = *(f4p)(src + (long)k * total); s0.x += a.x; s0.y += a.y; s0.z += a.z; s0.w += a.w; }
     }
     red[g][col] = make_float4((s0.x + s1.x) + (s2.x + s3.x), (s0.y + s1.y) + (s2.y + s3.y), (s0.z + s1.z) + (s2.z + s3.z), (s0.w + s1.w) + (s2.w + s3.w));
     __syncthreads();
-    if (g == 0 && i < total) {
+    if (writer) {
         float t[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int k = 0; k < G; ++k) { const float4 a = red[k][col]; t[0] += a.x; t[1] += a.y; t[2] += a.z; t[3] += a.w; }
-        const int kn0 = (int)(i % Cb); const long r = i / Cb;            // 4 consecutive kn of one (tap, kc): Cb % 4 == 0
-        const int kc = (int)(r % Ca); const int tap = (int)(r / Ca);
-        if (is_db) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) if (kn0 + j < kn_valid) db[kn0 + j] += t[j];
-        } else if (kc < kc_valid) {
-            float* o = dw + tap * s_tap + kc * s_kc;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) if (kn0 + j < kn_valid) o[(kn0 + j) * s_kn] += t[j];
-        }
+        for (int j = 0; j < 4; ++j) if (kn0 + j < kn_valid) o[j * s_o] = prior[j] + t[j];
     }
 }
 
