@@ -6,8 +6,9 @@
 // tensors, so do two passes of one network (pass A and the first VAT forward): between chap_group_begin() and chap_group_end()
 // the library records the launches per "lane" and then issues the j-th launch of every lane as ONE grid (gridDim.z = lanes) when
 // they resolved to the same kernel instance and launch geometry -- same blocks, same per-block work, same reduction slots, hence
-// bit-identical results to the one-by-one launches, with one fixed cost instead of 2-4.  Lanes that do not match are launched one
-// after the other in lane order.  (include/chap_hip.h: chap_group_begin / chap_group_next_lane / chap_group_end.)
+// bit-identical results to the one-by-one launches, with one fixed cost instead of 2-4.  Within a position the first lane not yet
+// issued takes every later matching lane with it (up to CHAP_MAX_LANES); what is left follows the same way, in lane order (A B A:
+// both A, then B).  (include/chap_hip.h: chap_group_begin / chap_group_next_lane / chap_group_end; tests/test_group_merge_cpu.py.)
 #pragma once
 #include <atomic>
 #include <cstring>

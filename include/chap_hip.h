@@ -648,8 +648,10 @@ int chap_grad_sim(const chap_gradsim_params* p, void* stream);
  * Between begin and end the entry points of the networks' forward / backward path (chap_conv_fwd, chap_conv_c1_*, chap_wgrad,
  * chap_bn_finalize, chap_bn_eval_affine, chap_act_bwd_*, chap_act_pool2, chap_upsample2x*, chap_planar_to_cl, chap_cl_to_planar,
  * chap_channel_sum, chap_keep_mask, chap_chan_mask, chap_fold_perturbed, chap_residual_fwd, chap_residual_bwd, chap_grad_sum) check their arguments and RECORD their launches instead
- * of issuing them; chap_group_end issues, for j = 0, 1, ..., the j-th recorded launch of every lane -- as ONE grid (gridDim.z = lanes,
- * up to 4) when they resolved to the same kernel instance and launch geometry, else one after the other in lane order.  Every block
+ * of issuing them; chap_group_end issues, for j = 0, 1, ..., the j-th recorded launch of every lane (lanes with fewer than j + 1
+ * launches sit the position out): the first lane not yet issued takes with it, as ONE grid (gridDim.z = lanes, up to 4), every later
+ * lane whose launch resolved to the same kernel instance, LDS size and launch geometry; the lanes left over follow the same way, in
+ * lane order (lanes A B A: the two A as one grid, then B; five equal lanes: four, then one).  Every block
  * does exactly the work it would do in a launch of its own (same tiles, same reduction slots): results are bit-identical to the
  * ungrouped calls.  The lanes must be independent of each other (no lane reads what another lane of the same region writes);
  * within a lane the order of the calls is kept.  All calls of a region go to the stream given to chap_group_begin; any other

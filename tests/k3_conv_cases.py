@@ -358,8 +358,8 @@ def deal_tiles(ntiles, nsplit):
 
 
 # ---- inputs and references ----------------------------------------------------------------------------------------------------------------------------------------
-def _gen(c, dt):
-    return torch.Generator().manual_seed(sum(map(ord, c["name"])) * 2 + DTYPE_ID[dt])
+def _gen(c, dt, lane=0):
+    return torch.Generator().manual_seed(sum(map(ord, c["name"])) * 2 + DTYPE_ID[dt] + sc.LANE_SEED * lane)
 
 
 def _sources(c, dt, kinds, chans, g):
@@ -400,8 +400,8 @@ def pack_args(c):
     return (K, M, taps) if c["kind"] == CF else (M, K, taps)
 
 
-def fwd_inputs(c, dt):
-    g = _gen(c, dt)
+def fwd_inputs(c, dt, lane=0):
+    g = _gen(c, dt, lane)
     K, M = k_channels(c), c["cout"]
     srcs = _sources(c, dt, c["src"], c["cin"], g)
     w = torch.randn(weight_shape(c), generator=g) / math.sqrt(K * 3 ** c["dims"])
@@ -520,8 +520,8 @@ def pixel_tile(c, dt):
 
 
 # ---- weight gradients ---------------------------------------------------------------------------------------------------------------------------------------------------
-def wgrad_inputs(c, dt):
-    g = _gen(c, dt)
+def wgrad_inputs(c, dt, lane=0):
+    g = _gen(c, dt, lane)
     Ne, sp = images(c)
     As = _sources(c, dt, c["A"], c["ca"], g)
     B = sc.make_source("p", Ne, c["cb"], sp, DTYPES[dt], g)

@@ -210,8 +210,11 @@ def _rq(x, dtype):
     return x.to(dtype).float()
 
 
-def _gen(c, dt):
-    return torch.Generator().manual_seed(sum(map(ord, c["name"])) * 2 + DTYPE_ID[dt])
+LANE_SEED = 100003                                         # lane k of a merged-grid case (tests/group_cases.py): the same shapes, another draw
+
+
+def _gen(c, dt, lane=0):
+    return torch.Generator().manual_seed(sum(map(ord, c["name"])) * 2 + DTYPE_ID[dt] + LANE_SEED * lane)
 
 
 def make_source(kind, N, C, sp, dtype, g):
@@ -258,8 +261,8 @@ def out_spatial(c):
     return tuple(2 * s for s in c["grid"]) if c["op"] == "d2s" else c["grid"]
 
 
-def fwd_inputs(c, dt):
-    dtype, g = DTYPES[dt], _gen(c, dt)
+def fwd_inputs(c, dt, lane=0):
+    dtype, g = DTYPES[dt], _gen(c, dt, lane)
     K, M = sum(c["cin"]), c["cout"]
     srcs = [make_source(kd, c["N"], ci, in_spatial(c), dtype, g) for kd, ci in zip(c["src"], c["cin"])]
     taps = 1 if c["op"] in ("k1", "head", "d2s") else 2 ** c["dims"]
@@ -387,8 +390,8 @@ def fwd_emulate(c, dt, inp, fault=None):
 
 
 # ---- weight gradients -------------------------------------------------------------------------------------------------------------------------------------
-def wgrad_inputs(c, dt):
-    dtype, g = DTYPES[dt], _gen(c, dt)
+def wgrad_inputs(c, dt, lane=0):
+    dtype, g = DTYPES[dt], _gen(c, dt, lane)
     a_sp = tuple(c["ks"] * s for s in c["grid"])
     A = make_source(c["A"], c["N"], c["ca"], a_sp, dtype, g)
     B = make_source(c["B"], c["N"], c["cb"], c["grid"], dtype, g)
