@@ -278,6 +278,22 @@ class SgdEmaParams(C.Structure):
     _fields_ = [("sgd", SgdParams), ("ema", _vp), ("coef", _vp)]
 
 
+MONITOR_SLOTS, MONITOR_MAX_SCALARS, MONITOR_HDR = 512, 16, 2       # CHAP_MONITOR_* of include/chap_hip_monitor.h
+
+
+class MonitorParams(C.Structure):
+    _fields_ = [("logits", _vp * 2), ("labels", _vp), ("ws", _vp), ("N", _i32), ("C", _i32), ("P", _i32), ("n_first", _i32)]
+
+
+class MonitorLabelsParams(C.Structure):
+    _fields_ = [("maps", _vp * 2), ("labels", _vp), ("ws", _vp), ("N", _i32), ("C", _i32), ("P", _i32), ("n_first", _i32)]
+
+
+class MonitorFinalizeParams(C.Structure):
+    _fields_ = [("ws", _vp), ("ring", _vp), ("slot_iter", _vp), ("scalars", _vp * MONITOR_MAX_SCALARS),
+                ("C", _i32), ("ring_rows", _i32), ("nscalars", _i32), ("has_labels", _i32)]
+
+
 _SIGS = {  # name -> (restype, params struct or None)
     "chap_conv_fwd": ConvParams, "chap_pack_weights": PackParams, "chap_conv_c1_fwd": ConvC1Params,
     "chap_conv_c1_bwd": ConvC1BwdParams, "chap_wgrad": WgradParams, "chap_bn_finalize": BnFinalizeParams,
@@ -299,6 +315,9 @@ _SIGS = {  # name -> (restype, params struct or None)
 }
 # opt-in entry points declared in include/chap_hip_ext.h (same calling convention as _SIGS): not part of the default iteration
 _SIGS_EXT = {"chap_sgd_ema_step": SgdEmaParams}
+# the training monitor, declared in include/chap_hip_monitor.h (same calling convention): issued only with a chap_amd.monitor.StepMonitor attached
+_SIGS_MONITOR = {"chap_monitor_accumulate": MonitorParams, "chap_monitor_accumulate_labels": MonitorLabelsParams,
+                 "chap_monitor_finalize": MonitorFinalizeParams}
 _SIZE_FNS = {"chap_pack_size": PackParams, "chap_conv_c1_bwd_ws": ConvC1BwdParams, "chap_wgrad_ws": WgradParams,
              "chap_lcc_ws": LccParams, "chap_metrics_ws": MetricsParams}
 
@@ -349,8 +368,8 @@ def _fn(name):
             fn = getattr(L, name)
         except AttributeError:
             raise ChapError("libchap_hip.so does not export %s (stale build?)" % name)
-        if name in _SIGS or name in _SIGS_EXT:
-            fn.restype, fn.argtypes = C.c_int, [C.POINTER(_SIGS.get(name) or _SIGS_EXT[name]), _vp]
+        if name in _SIGS or name in _SIGS_EXT or name in _SIGS_MONITOR:
+            fn.restype, fn.argtypes = C.c_int, [C.POINTER(_SIGS.get(name) or _SIGS_EXT.get(name) or _SIGS_MONITOR[name]), _vp]
         else:
             fn.restype, fn.argtypes = _sz, [C.POINTER(_SIZE_FNS[name])]
         _bound[name] = fn

@@ -584,6 +584,58 @@ def sgd_ema_step(param, grad, mom, lr_dev, momentum, weight_decay, ema, coef_dev
 
 
 # ------------------------------------------------------------------------------------------
+# training monitor (include/chap_hip_monitor.h; chap_amd.monitor.StepMonitor owns the workspace and the ring)
+def monitor_group_words(C):
+    return 8 + 5 * C                    # CHAP_MONITOR_GROUP_WORDS
+
+
+def monitor_label_words(C):
+    return 4 * C                        # CHAP_MONITOR_LABEL_WORDS
+
+
+def monitor_row_words(C):
+    return 1 + 2 * monitor_group_words(C) + 2 * monitor_label_words(C) + L.MONITOR_MAX_SCALARS       # CHAP_MONITOR_ROW_WORDS
+
+
+def monitor_label_region(C):
+    return L.MONITOR_HDR + 2 * L.MONITOR_SLOTS * monitor_group_words(C)      # CHAP_MONITOR_LABEL_REGION
+
+
+def monitor_ws_words(C):
+    return monitor_label_region(C) + L.MONITOR_HDR + 2 * L.MONITOR_SLOTS * monitor_label_words(C)     # CHAP_MONITOR_WS_WORDS
+
+
+def monitor_accumulate(logits1, logits2, labels, ws, n_first):
+    """Counts of acc_conf_analysis (train_ours_2D.py:152-193) for two heads' fp32 planar logits [N, C, *sp] against int64 labels [N, *sp]:
+    one partial row per block into the logits region of `ws` (int64 / fp64 words).  Samples [0, n_first) are group 0, the rest group 1."""
+    p = L.MonitorParams()
+    p.logits[0], p.logits[1], p.labels, p.ws = logits1.data_ptr(), logits2.data_ptr(), labels.data_ptr(), ws.data_ptr()
+    p.N, p.C, p.P, p.n_first = logits1.shape[0], logits1.shape[1], logits1[0, 0].numel(), n_first
+    L.call("chap_monitor_accumulate", p, _stream())
+
+
+def monitor_accumulate_labels(map1, map2, labels, ws, n_first, num_classes):
+    """The Dice terms (inter_f, pred_f) of two int64 label maps [N, *sp] against `labels`, into the label-map region of `ws`."""
+    p = L.MonitorLabelsParams()
+    p.maps[0], p.maps[1], p.labels, p.ws = map1.data_ptr(), map2.data_ptr(), labels.data_ptr(), ws.data_ptr()
+    p.N, p.C, p.P, p.n_first = map1.shape[0], num_classes, map1[0].numel(), n_first
+    L.call("chap_monitor_accumulate_labels", p, _stream())
+
+
+def monitor_finalize(ws, ring, slot_iter, num_classes, scalars=(), has_labels=True):
+    """Fixed-order totals of the partial rows -> row slot_iter[0] % len(ring) of `ring` (fp64 [R, monitor_row_words(C)]), stamped with the
+    iteration slot_iter[1]; `scalars`: up to 16 one-element fp32 device tensors (or views) copied into the row."""
+    p = L.MonitorFinalizeParams()
+    p.ws, p.ring, p.slot_iter = ws.data_ptr(), ring.data_ptr(), slot_iter.data_ptr()
+    if len(scalars) > L.MONITOR_MAX_SCALARS:
+        raise ValueError("monitor_finalize: %d scalars (at most %d)" % (len(scalars), L.MONITOR_MAX_SCALARS))
+    for k, t in enumerate(scalars):
+        p.scalars[k] = t.data_ptr()
+    p.C, p.ring_rows, p.nscalars, p.has_labels = num_classes, ring.shape[0], len(scalars), int(has_labels)
+    L.call("chap_monitor_finalize", p, _stream())
+
+
+# ------------------------------------------------------------------------------------------
 # inference callers (val_2D.py:54-97, test_3D_util.py:14-79)
 ENSEMBLE_MODES = {"model1": 0, "model2": 1, "logit_ensemble": 2, "prob_ensemble": 3}
 

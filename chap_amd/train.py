@@ -288,7 +288,9 @@ class ChapStep:
     The BCP box offsets, LR and consistency weight live in device memory so that the whole iteration
     can be captured once as a HIP graph (`capture()`) and replayed."""
 
-    def __init__(self, model, args=None, optimizer=None, world_size=1, teacher=None):
+    MONITOR_LAYOUT = "chap"         # what the scalar words of a monitor row hold (chap_amd.monitor.SCALAR_LAYOUTS)
+
+    def __init__(self, model, args=None, optimizer=None, world_size=1, teacher=None, monitor=None):
         a = dict(DEFAULT_ARGS)
         a.update(args or {})
         self.args, self.model = a, model
@@ -297,10 +299,18 @@ class ChapStep:
         dev = self.opt.lr_dev.device
         self.dims = getattr(model, "dims", 2)
         # host-scheduled values of an iteration in ONE device word block -> one host-to-device copy per step:
-        # [BCP box: 4 / 6 int32 | consistency weight f32 | learning rate f32], and with a mean teacher [| a f32 | b f32] of its average behind them
+        # [BCP box: 4 / 6 int32 | consistency weight f32 | learning rate f32], and with a mean teacher [| a f32 | b f32] of its average behind them,
+        # and with a monitor [| ring slot int32 | iteration int32] of the row its finalize kernel writes behind those
         nbox = 4 if self.dims == 2 else 6
         self.teacher = teacher
         nsched = 8 if teacher is None else 10
+        self.monitor = monitor
+        if monitor is not None:
+            if monitor.C != a["num_classes"] or monitor.ws is None or monitor.ws.device != dev:
+                raise ValueError("chap_amd ChapStep: the monitor was built for %d classes on %s, the step runs %d on %s" % (monitor.C, monitor.device, a["num_classes"], dev))
+            monitor.scalar_layout = self.MONITOR_LAYOUT
+            self._mon_at = nsched
+            nsched += 2
         self._sched = torch.zeros(nsched, dtype=torch.int32, device=dev)
         self._sched_pin = [torch.empty(nsched, dtype=torch.int32).pin_memory() for _ in range(4)]      # host side of the schedule block (see _upload_sched)
         self._sched_ev, self._sched_k = [None] * 4, 0
@@ -409,6 +419,8 @@ class ChapStep:
         vals = list(box_vals) + [0] * (6 - len(box_vals)) + [f2i(cw), f2i(self.opt.param_groups[0]["lr"])]
         if self.teacher is not None:            # global_step of update_ema_variables (train_ours_2D.py:50-54) = iter_num before finish() counts this step
             vals += [f2i(c) for c in ema_coefficients(self.iter_num, self.opt.ema_decay)]
+        if self.monitor is not None:            # the row of this iteration: its ring slot, and the number the reference's log line prints (iter_num + 1, train_ours_2D.py:385,404-405)
+            vals += [self.monitor.next_slot(), self.iter_num + 1]
         # Through a small ring of PINNED host blocks, asynchronously: a plain `copy_` from pageable memory synchronises the stream,
         # i.e. the host would wait for the previous iteration to drain before it even starts launching the next one (the GPU then
         # idles while the graph's first nodes are being submitted: ~0.5 ms of gaps at the head of every replay in the kernel trace).
@@ -427,6 +439,8 @@ class ChapStep:
         """poly LR applied AFTER the step (train_ours_2D.py:385-389)."""
         a = self.args
         self.iter_num += 1
+        if self.monitor is not None:
+            self.monitor.advance()
         lr_ = a["base_lr"] * (1.0 - self.iter_num / a["max_iterations"]) ** 0.9
         if isinstance(self.opt, FusedSGD):
             self.opt.param_groups[0]["lr"] = float(lr_)          # reaches the device with the next step's schedule block
@@ -508,9 +522,24 @@ class ChapStep:
         out = {"mix_losses": losses, "vat_loss": vat_loss}
         if self.args["dropout"]:        # (behind _decoder_fork's join: the fp branch never forks its second decoder under capture)
             out["fp_losses"] = self._fp_branch(ctx["uimg_ab"], ctx["pseudo_outputs1"], ctx["pseudo_outputs2"], ctx["inject"], None)
+        if self.monitor is not None:    # behind the join of pass B's stream above: both accumulate launches and every loss word are complete
+            self._monitor_finalize([l[j:j + 1] for l in losses for j in range(3)] + [vat_loss])
         if update:
             self.exchange_and_update()
         return out
+
+    # ------------------------------------------------------------------ training monitor (chap_amd.monitor; every launch below only with one attached)
+    def _monitor_logits(self, logits1, logits2, labels, n_first):
+        """Behind pseudo_block, on its stream: the counts of the two heads' arg-max maps against the samples' own labels."""
+        ops.monitor_accumulate(logits1, logits2, labels, self.monitor.ws, n_first)
+
+    def _monitor_maps(self, map1, map2, labels, n_first):
+        """Behind largest_cc, on pass B's stream: the Dice terms of the filtered maps.  Writes its own region of the workspace."""
+        ops.monitor_accumulate_labels(map1, map2, labels, self.monitor.ws, n_first, self.args["num_classes"])
+
+    def _monitor_finalize(self, scalars, has_labels=True):
+        m = self.monitor
+        ops.monitor_finalize(m.ws, m.ring, self._sched[self._mon_at:self._mon_at + 2], m.C, scalars, has_labels)
 
     @contextlib.contextmanager
     def _decoder_fork(self, origin):
@@ -571,6 +600,9 @@ class ChapStep:
         with self._forks(FORK_PASS_A), torch.no_grad():
             pre_ab1, pre_ab2 = model(ctx["uimg_ab"], drop_masks=inject.get("drop_A"))
             soft1, soft2, pseudo1, pseudo2, knowledge = ops.pseudo_block(pre_ab1, pre_ab2)
+            if self.monitor is not None:        # the unlabelled samples' labels are in every batch (the reference's ulab_a / ulab_b)
+                ctx["ulab"] = label_batch[lbs:]
+                self._monitor_logits(pre_ab1, pre_ab2, ctx["ulab"], 0)
         if pre is not None:
             main.wait_stream(pre)
         ctx.update(outputs_soft1=soft1, outputs_soft2=soft2, pseudo_outputs1=pseudo1, pseudo_outputs2=pseudo2, knowledge=knowledge)
@@ -598,6 +630,8 @@ class ChapStep:
                 plab2 = ops.largest_cc(ctx["pseudo_outputs2"], nc)
             else:
                 plab1, plab2 = ctx["pseudo_outputs1"], ctx["pseudo_outputs2"]
+            if self.monitor is not None:
+                self._monitor_maps(plab1, plab2, ctx["ulab"], 0)
             loss_mask = torch.empty(lsub, *volume_batch.shape[2:], dtype=torch.int64, device=volume_batch.device)
             # BCP mixing (:335-338): net_input_mix = cat(net_input_l, net_input_unl)
             net_input_mix = torch.empty((lsub + usub,) + tuple(volume_batch.shape[1:]), dtype=torch.float32, device=volume_batch.device)
@@ -727,6 +761,7 @@ class ChapStep:
         self._static_v = volume_batch.clone()
         self._static_l = label_batch.clone()
         snap = self.state_dict() if (restore and warmup > 0) else None
+        mon_snap = self.monitor.snapshot() if (snap is not None and self.monitor is not None) else None
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
@@ -738,6 +773,8 @@ class ChapStep:
         torch.cuda.synchronize()
         if snap is not None:
             self.load_state_dict(snap)
+            if mon_snap is not None:            # the warm-up iterations' rows go with their updates
+                self.monitor.restore(mon_snap)
             torch.cuda.synchronize()
         self.model._rng.reset_counter()
         np_state = np.random.get_state()
@@ -792,6 +829,8 @@ class ChapStep:
                 out["fp_losses"] = self._fp_branch(ctx["uimg_ab"], ctx["pseudo_outputs1"], ctx["pseudo_outputs2"], ctx["inject"], None)
         stack.close()
         with torch.cuda.graph(gO, **kw):
+            if self.monitor is not None:        # graphs B and V have both run when this one is replayed
+                self._monitor_finalize([l[j:j + 1] for l in losses for j in range(3)] + [vat_loss])
             self.opt.step(grad_scale=1.0 / self.world_size, grad2=self.grad2)
         self._dp_ctx, self._static_out = ctx, out
         self._graph, self._graph_opt, self._graphs_dp = None, None, (gA, gB, gV, gO)
@@ -877,7 +916,10 @@ class AblationStep(ChapStep):
     SGD + poly LR.  `losses.DiceLoss` is absent upstream: the SSL4MIS definition (1 - (2 sum p t + s)/(sum p^2 + sum t +
     s), s = 1e-5, mean over classes) is used.  The shipped VAT call passes the full-batch soft outputs next to an
     unlabeled-half mask (shape-inconsistent); here, as in the main loop, VAT acts on the unlabeled half.  fp_loss (the
-    `dropout` branch, :209-213) is 0 as upstream.  The consistency weight lives in device memory: capture()/replay() work."""
+    `dropout` branch, :209-213) is 0 as upstream.  The consistency weight lives in device memory: capture()/replay() work.
+    With a monitor: the full-batch forward is scored with n_first = labeled_bs, acc_conf_analysis's split (train_ours_2D.py:157-158)."""
+
+    MONITOR_LAYOUT = "ablation"
 
     def _iteration(self, volume_batch, label_batch, inject=None, update=True):
         a, model = self.args, self.model
@@ -886,6 +928,8 @@ class AblationStep(ChapStep):
         out1, out2 = model(volume_batch, drop_masks=inject.get("drop_F"))
         with torch.no_grad():
             soft1, soft2, arg1, arg2, knowledge = ops.pseudo_block(out1[lbs:].contiguous(), out2[lbs:].contiguous())
+            if self.monitor is not None:
+                self._monitor_logits(out1, out2, label_batch, lbs)
         d1, d2 = torch.empty_like(out1), torch.empty_like(out2)
         lab = label_batch[:lbs].contiguous()
         sup, cps = [], []
@@ -904,6 +948,8 @@ class AblationStep(ChapStep):
             diff_mask = ops.diff_mask(arg1, arg2, knowledge, 4, a["topk1"])
             vat_loss = self.adv_loss(model, volume_batch, soft1, soft2, diff_mask, a["adv_losstype"], weight_dev=self.cw_dev,
                                      inject=inject, grad_buffer=self.grad2, weight=a.get("w_adv", 1.0))
+        if self.monitor is not None:
+            self._monitor_finalize(sup + cps + [vat_loss], has_labels=False)
         if update:
             self.exchange_and_update()
         return {"sup_losses": sup, "cps_losses": cps, "vat_loss": vat_loss, "consistency_weight": self._cw_host}

@@ -1,7 +1,8 @@
 """train(args, snapshot_path): the thin host loop around the MI355X iteration, with the reference's entry-point
 signature and outputs (code/train_ours_2D.py:219-463): `args` is the dict of its argparse flags (`vars(args)`, :525-526);
 it writes `latest.pth` and `{model}_best_model.pth` (= torch.save(model.state_dict()), :428-435), `val.csv` (:437-449)
-and `log.txt` (:567-570) under `snapshot_path`.
+and `log.txt` (:567-570) under `snapshot_path`.  `args["monitor"]` (default off; chap_amd.monitor) adds `monitor.csv`, one line per
+iteration, and the reference's per-iteration `l loss` / `unl loss` line (:404-405) to `log.txt`, both written once per validation interval.
 
 What is NOT here (out of scope): TensorBoard / wandb, the validation-set reader.  The data layer is an
 argument: `args["trainloader"]` / `args["val_volumes"]` may carry any iterable of {'image': [B,1,H,W] fp32, 'label': [B,H,W]}
@@ -19,13 +20,15 @@ import numpy as np
 import torch
 
 from .inference import test_single_volume
+from .monitor import StepMonitor, flush_to_run
 from .networks.net_factory import net_factory
 from .synthetic import synthetic_batch
 from .train import DEFAULT_ARGS, ChapStep, build_teacher, check_num_classes
 
 FLAG_DEFAULTS = dict(DEFAULT_ARGS, model="dualdecoder", decoder_type="mcnet", gpu=0, seed=1337, image_size=[256, 256],
                      val_interval=200, labeled_num=7, use_graph=True,          # train_ours_2D.py:469-526
-                     mean_teacher=False, ema_decay=0.99)                       # --ema_decay (:499); mean_teacher: the commented-out ema_model (:251)
+                     mean_teacher=False, ema_decay=0.99,                       # --ema_decay (:499); mean_teacher: the commented-out ema_model (:251)
+                     monitor=False)                                            # chap_amd.monitor: monitor.csv and the loss line of :404-405
 
 
 def _synthetic_loader(a):
@@ -54,11 +57,14 @@ def train(args, snapshot_path):
     model.train()
     if a.get("dtype", "fp32") == "bf16":
         model.set_compute_dtype(torch.bfloat16)
+    # monitor: per-iteration pseudo-label quality from inside the step (chap_amd.monitor), read every val_interval iterations
+    mon = StepMonitor(a["num_classes"], ring=max(256, int(a["val_interval"])), device=device) if a["monitor"] else None
+    mon_kw = {} if mon is None else {"monitor": mon}
     if a["mean_teacher"]:                                                        # ema_model = create_model(ema=True) (:238-251)
         teacher = build_teacher(make).eval()
-        step = ChapStep(model, a, teacher=teacher)
+        step = ChapStep(model, a, teacher=teacher, **mon_kw)
     else:
-        teacher, step = None, ChapStep(model, a)
+        teacher, step = None, ChapStep(model, a, **mon_kw)
     loader = a.get("trainloader")
     if loader is None and a.get("root_path") and a.get("labeled_slices"):
         from .data import DeviceLoader, SliceStore
@@ -124,6 +130,8 @@ def train(args, snapshot_path):
                     torch.save(teacher.state_dict(), os.path.join(snapshot_path, "{}_ema_best_model.pth".format(a["model"])))
                 log.info("iteration %d : ema_mean_dice : %f ema_mean_hd95 : %f" % (it, ema_dice, ema_hd95))
             model.train()
+        if mon is not None and (it % a["val_interval"] == 0 or it >= a["max_iterations"]):
+            flush_to_run(mon, snapshot_path, log)
         if it >= a["max_iterations"]:
             break
         if device_fed:

@@ -19,6 +19,7 @@ import time
 import numpy as np
 import torch
 
+from .monitor import StepMonitor, flush_to_run
 from .networks.net_factory_3d import net_factory_3d
 from .networks.vnet import DualDecoder3d, VNet
 from .synthetic import synthetic_batch_3d
@@ -27,7 +28,7 @@ from .train import DEFAULT_ARGS, ChapStep, build_teacher, check_num_classes
 
 FLAG_DEFAULTS = dict(DEFAULT_ARGS, model="dualdecoder", num_classes=2, patch_size=[112, 112, 80], batch_size=4, labeled_bs=2,
                      stride_xy=18, stride_z=4, val_interval=200, use_graph=True, gpu=0, seed=1337,
-                     mean_teacher=False, ema_decay=0.99)       # as train_ours_2D: --ema_decay (train_ours_2D.py:499), the ema_model of :251
+                     mean_teacher=False, ema_decay=0.99, monitor=False)       # as train_ours_2D: --ema_decay (train_ours_2D.py:499), the ema_model of :251
 
 
 def _synthetic_loader(a):
@@ -66,11 +67,14 @@ def train(args, snapshot_path):
         model.train()
         if a.get("dtype", "fp32") == "bf16":
             model.set_compute_dtype(torch.bfloat16)
+        # monitor: per-iteration pseudo-label quality from inside the step (chap_amd.monitor), read every val_interval iterations
+        mon = StepMonitor(a["num_classes"], ring=max(256, int(a["val_interval"])), device=device) if a["monitor"] else None
+        mon_kw = {} if mon is None else {"monitor": mon}
         if a["mean_teacher"]:                   # ema_model = create_model(ema=True) (train_ours_2D.py:238-251)
             teacher = build_teacher(make).eval()
-            step = ChapStep(model, a, teacher=teacher)
+            step = ChapStep(model, a, teacher=teacher, **mon_kw)
         else:
-            teacher, step = None, ChapStep(model, a)
+            teacher, step = None, ChapStep(model, a, **mon_kw)
         loader = a.get("trainloader")
         if loader is None and a.get("root_path") and a.get("labeled_num"):
             from .data import DeviceLoader, VolumeStore
@@ -130,6 +134,8 @@ def train(args, snapshot_path):
                         torch.save(teacher.state_dict(), os.path.join(snapshot_path, "{}_ema_best_model.pth".format(a["model"])))
                     log.info("iteration %d : ema_dice_score : %f" % (it, ema_dice))
                 model.train()
+            if mon is not None and (it % a["val_interval"] == 0 or it >= a["max_iterations"]):
+                flush_to_run(mon, snapshot_path, log)
             if it >= a["max_iterations"]:
                 break
             if device_fed:
