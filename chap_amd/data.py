@@ -167,11 +167,20 @@ class DeviceLoader:
     buffers on the current stream (ChapStep.stage_from).  `last_draws`: the draws of the last batch, one dict per sample.
     A VolumeStore gives the 3D transform with output_size = the patch [P0, P1, P2].  `pad=True` (VolumeStore only): a volume with an axis
     not larger than the crop is zero-padded on every axis before the crop (the public LA RandomCrop rule, DESIGN.md "3D workflow")
-    instead of being refused; the draws then carry a `pad` tuple and `corner` is in padded coordinates."""
+    instead of being refused; the draws then carry a `pad` tuple and `corner` is in padded coordinates.
+    `rank`, `world` (data-parallel, DESIGN.md section 6 "train() on several ranks"): `batch_size` and `labeled_bs` are PER RANK.  Every rank
+    runs the sampler and the augmentation draws of the GLOBAL batch (world * labeled_bs labelled, then world * (batch_size - labeled_bs)
+    unlabelled items) from the same seed, in today's order, and keeps its own contiguous block [rank * n, (rank + 1) * n) of each group: the
+    ranks' batches, concatenated labelled-first, are the batches of the world=1 loader of world * batch_size / world * labeled_bs.  The device
+    side is one launch of batch_size records, as without ranks.  `last_draws`: the rank's own samples; `last_global_indices`: the store
+    indices of the whole global batch."""
     RING = 4
 
-    def __init__(self, store, labeled_idxs, unlabeled_idxs, batch_size, labeled_bs, output_size, seed=0, pad=False):
+    def __init__(self, store, labeled_idxs, unlabeled_idxs, batch_size, labeled_bs, output_size, seed=0, pad=False, rank=0, world=1):
         self.store, self.batch_size, self.labeled_bs = store, int(batch_size), int(labeled_bs)
+        self.rank, self.world = int(rank), int(world)
+        if self.world < 1 or not 0 <= self.rank < self.world:
+            raise ValueError("DeviceLoader: rank=%d outside [0, world=%d)" % (self.rank, self.world))
         self.pad = bool(pad)
         if self.pad and store.ndim != 3:
             raise ValueError("DeviceLoader: pad=True is the 3D crop's padding; the store is %dD" % store.ndim)
@@ -189,7 +198,10 @@ class DeviceLoader:
             if small:
                 raise ValueError("DeviceLoader: volume %d of shape %s is smaller than the crop %s of patch %s"
                                  % (small[0], tuple(store.shapes[small[0]]), need, p))
-        self.sampler = TwoStreamBatchSampler(labeled_idxs, unlabeled_idxs, batch_size, self.batch_size - self.labeled_bs, seed)
+        self.sampler = TwoStreamBatchSampler(labeled_idxs, unlabeled_idxs, self.world * self.batch_size, self.world * (self.batch_size - self.labeled_bs), seed)
+        lbs, ubs = self.labeled_bs, self.batch_size - self.labeled_bs
+        # positions of this rank's samples in the global batch: its block of the labelled group, then its block of the unlabelled one
+        self._own = [self.rank * lbs + j for j in range(lbs)] + [self.world * lbs + self.rank * ubs + j for j in range(ubs)]
         self.rng = np.random.default_rng([int(seed), 1])          # the augmentation draws: a stream of their own
         self._rec_t = L.Augment2dRecord if store.ndim == 2 else (L.Augment3dPadRecord if self.pad else L.Augment3dRecord)
         nbytes = ctypes.sizeof(self._rec_t) * self.batch_size
@@ -201,7 +213,7 @@ class DeviceLoader:
         self._dev = [torch.empty(nbytes, dtype=torch.uint8, device=store.device) for _ in range(self.RING)]
         self._ev, self._slot = [None] * self.RING, 0
         self._endless = self._eternal()
-        self.last_draws = None
+        self.last_draws, self.last_global_indices = None, None
 
     def __len__(self):
         return len(self.sampler)
@@ -223,8 +235,20 @@ class DeviceLoader:
         self._launch(next(self._endless), image_out, label_out)
 
     def _draw(self, idxs):
+        """Records and draws of this rank's samples of the (global) batch `idxs`.  The draws are made for EVERY sample of the global batch, in
+        its order: the augmentation stream advances on all ranks alike."""
+        recs, draws = self._draw_all(idxs)
+        self.last_global_indices = [int(i) for i in idxs]
+        if self.world == 1:
+            return recs, draws
+        own = (self._rec_t * self.batch_size)()
+        for j, g in enumerate(self._own):
+            own[j] = recs[g]
+        return own, [draws[g] for g in self._own]
+
+    def _draw_all(self, idxs):
         st = self.store
-        recs = (self._rec_t * self.batch_size)()
+        recs = (self._rec_t * len(idxs))()
         draws = []
         for r, i in zip(recs, idxs):
             r.offset = int(st.offsets[i])
@@ -259,7 +283,7 @@ class DeviceLoader:
         return recs, draws
 
     def _launch(self, idxs, image_out, label_out):
-        if len(idxs) != self.batch_size or image_out.shape[0] != self.batch_size or tuple(image_out.shape[2:]) != self.output_size:
+        if len(idxs) != self.world * self.batch_size or image_out.shape[0] != self.batch_size or tuple(image_out.shape[2:]) != self.output_size:
             raise ValueError("DeviceLoader: output buffer %s for batches of %d x %s" % (tuple(image_out.shape), self.batch_size, self.output_size))
         if self._pin[0] is None:
             raise RuntimeError("DeviceLoader: the store lives on %s; batches are built by a GPU kernel (a host-resident store serves _draw only)" % self.store.device)

@@ -834,3 +834,7 @@ class Rng:
 
     def reset_counter(self):
         self.count = 0
+
+    def rebase(self, seed, rank=0):
+        """The stream of data-parallel rank `rank` under `seed`; rank 0 keeps the base the constructor gives."""
+        self.base = (int(seed) + 0x9E3779B1 * int(rank)) & 0xFFFFFFFF

@@ -170,8 +170,38 @@ def flush_to_run(monitor, snapshot_path, log):
     """read() the ring and append what came back to the run's files: one line per iteration to <snapshot>/monitor.csv, and the reference's
     'iteration %d : l loss : %f unl loss : %f' (train_ours_2D.py:404-405) to the log.  The train() entries call it every val_interval
     iterations and at the end; the lines of an interval therefore arrive together."""
+    return write_rows(monitor.read(), snapshot_path, log)
+
+
+_SUMMED = ("n", "n_disagree", "gt", "n_correct", "conf_correct", "conf_err", "inter", "pred", "inter_f", "pred_f")
+
+
+def merge_rows(list_of_rows):
+    """The read() results of the data-parallel ranks, one per rank and for the same iterations, as ONE: counts and confidence sums are added (the
+    rows of the global batch), the scalar loss words -- each rank's mean over its own samples -- are averaged, 'dropped' is the largest.  The
+    iteration words must agree (every rank flushes at the same iterations); ValueError otherwise."""
+    if len(list_of_rows) == 0:
+        raise ValueError("chap_amd monitor: merge_rows of no rows")
+    first = list_of_rows[0]
+    its = np.asarray(first["iteration"], dtype=np.int64)
+    for r, rows in enumerate(list_of_rows[1:], 1):
+        other = np.asarray(rows["iteration"], dtype=np.int64)
+        if other.shape != its.shape or (other != its).any():
+            raise ValueError("chap_amd monitor: merge_rows: rank %d holds iterations %s, rank 0 holds %s" % (r, other.tolist(), its.tolist()))
+        if rows.get("scalar_layout") != first.get("scalar_layout"):
+            raise ValueError("chap_amd monitor: merge_rows: rank %d has scalar layout %r, rank 0 %r" % (r, rows.get("scalar_layout"), first.get("scalar_layout")))
+    out = {"iteration": its.copy(), "scalar_layout": first.get("scalar_layout", "chap"), "dropped": max(int(rows.get("dropped", 0)) for rows in list_of_rows)}
+    for name in _SUMMED + ("scalars",):
+        acc = np.array(first[name], dtype=np.float64)
+        for rows in list_of_rows[1:]:
+            acc = acc + np.asarray(rows[name], dtype=np.float64)
+        out[name] = acc / len(list_of_rows) if name == "scalars" else acc
+    return out
+
+
+def write_rows(rows, snapshot_path, log):
+    """flush_to_run's writing half, for rows that are already read (one process's, or merge_rows of the ranks')."""
     import os
-    rows = monitor.read()
     d = StepMonitor.derive(rows)
     path = os.path.join(snapshot_path, "monitor.csv")
     new = not os.path.exists(path)

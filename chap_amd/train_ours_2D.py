@@ -10,7 +10,16 @@ dicts / list of (image [1,S,H,W], label [1,S,H,W]) tensors (what the reference's
 `next_into` (chap_amd.data.DeviceLoader: slices resident on the device, RandomGenerator as one kernel per batch) feeds the
 captured iteration through ChapStep.stage_from; `args["root_path"]` + `args["labeled_slices"]` (the number of labelled slices at
 the head of `train_slices.list`; the reference's patient -> slice table is not copied) build that loader from the ACDC h5 layout.
-With none of them the fixed-seed synthetic generator of chap_amd.synthetic stands in."""
+With none of them the fixed-seed synthetic generator of chap_amd.synthetic stands in.
+
+`args["data_parallel"]` (default off; chap_amd.distributed, DESIGN.md section 6 "train() on several ranks"): this process is ONE RANK of the
+run, started by `python -m chap_amd.launch` or `torch.distributed.run`.  `batch_size` / `labeled_bs` are per rank; the DeviceLoader built
+here is the rank's shard of the global batch (a loader passed in `trainloader` is taken as already being the rank's own); gradients go
+through the fold schedule of chap_amd.parallel; at a validation interval the replicas are checked for equality, rank 0's BatchNorm statistics
+are broadcast, every rank scores val_volumes[rank::world] and the mean is taken over the gathered per-volume values in volume order, so every
+rank takes the same "best" decision; rank 0 alone writes files (a barrier follows).  The loss line of every 50th iteration stays rank 0's
+LOCAL values (its own shard); the monitor's rows are merged over the ranks (monitor.merge_rows).  `dp_backend` ("nccl" | "gloo": all
+ranks on cuda:`gpu`, the one-GPU rehearsal), `dp_timeout_s`, `dp_force_group` (a 1-rank group), `dp_noise_per_rank` (default True)."""
 import csv
 import logging
 import os
@@ -19,8 +28,9 @@ import time
 import numpy as np
 import torch
 
+from .distributed import attach_step, flush_monitor, init_rank, sync_for_validation
 from .inference import test_single_volume
-from .monitor import StepMonitor, flush_to_run
+from .monitor import StepMonitor
 from .networks.net_factory import net_factory
 from .synthetic import synthetic_batch
 from .train import DEFAULT_ARGS, ChapStep, build_teacher, check_num_classes
@@ -28,13 +38,14 @@ from .train import DEFAULT_ARGS, ChapStep, build_teacher, check_num_classes
 FLAG_DEFAULTS = dict(DEFAULT_ARGS, model="dualdecoder", decoder_type="mcnet", gpu=0, seed=1337, image_size=[256, 256],
                      val_interval=200, labeled_num=7, use_graph=True,          # train_ours_2D.py:469-526
                      mean_teacher=False, ema_decay=0.99,                       # --ema_decay (:499); mean_teacher: the commented-out ema_model (:251)
-                     monitor=False)                                            # chap_amd.monitor: monitor.csv and the loss line of :404-405
+                     monitor=False,                                            # chap_amd.monitor: monitor.csv and the loss line of :404-405
+                     data_parallel=False, dp_backend="nccl", dp_timeout_s=600, dp_force_group=False, dp_noise_per_rank=True)      # chap_amd.distributed
 
 
-def _synthetic_loader(a):
+def _synthetic_loader(a, rank=0):
     h, w = a["image_size"]
     lbs, ubs = a["labeled_bs"], a["batch_size"] - a["labeled_bs"]
-    pool = [synthetic_batch(a["seed"] + i, lbs, ubs, h, w, a["num_classes"]) for i in range(8)]
+    pool = [synthetic_batch(a["seed"] + 8 * rank + i, lbs, ubs, h, w, a["num_classes"]) for i in range(8)]      # a pool of its own per data-parallel rank
     while True:
         for v, l in pool:
             yield {"image": v, "label": l}
@@ -44,14 +55,31 @@ def train(args, snapshot_path):
     a = dict(FLAG_DEFAULTS)
     a.update(args)
     check_num_classes(a["num_classes"], "chap_amd.train_ours_2D")
-    os.makedirs(snapshot_path, exist_ok=True)
+    ctx = init_rank(a)                          # the plain single process unless args["data_parallel"]
     log = logging.getLogger("chap_amd.train")
     log.setLevel(logging.INFO)
-    fh = logging.FileHandler(os.path.join(snapshot_path, "log.txt"))
-    log.addHandler(fh)
-    device = torch.device("cuda", a["gpu"])
+    fh = None
+    try:
+        if ctx.is_main:                         # rank 0 alone writes under snapshot_path
+            os.makedirs(snapshot_path, exist_ok=True)
+            fh = logging.FileHandler(os.path.join(snapshot_path, "log.txt"))
+            log.addHandler(fh)
+        model = _run(a, snapshot_path, ctx, log)
+        ctx.barrier()
+    finally:                    # also when the loop raises: leave the process groups, and a later train() in this process must not log into this file
+        ctx.close()
+        if fh is not None:
+            log.removeHandler(fh)
+            fh.close()
+    return model
+
+
+def _run(a, snapshot_path, ctx, log):
+    device = ctx.device
+    if ctx.group is not None:
+        torch.cuda.set_device(device)
     torch.manual_seed(a["seed"])
-    np.random.seed(a["seed"])
+    np.random.seed(a["seed"])                   # on every rank: ONE BCP box per iteration for the global batch, as the reference draws one per iteration
     make = lambda: net_factory(net_type=a["model"], in_chns=1, class_num=a["num_classes"], device=device, args=a)      # :240
     model = make()
     model.train()
@@ -59,19 +87,23 @@ def train(args, snapshot_path):
         model.set_compute_dtype(torch.bfloat16)
     # monitor: per-iteration pseudo-label quality from inside the step (chap_amd.monitor), read every val_interval iterations
     mon = StepMonitor(a["num_classes"], ring=max(256, int(a["val_interval"])), device=device) if a["monitor"] else None
-    mon_kw = {} if mon is None else {"monitor": mon}
+    step_kw = {} if mon is None else {"monitor": mon}
+    if ctx.group is not None:                   # one replica of several: the fused SGD scales the summed gradient by 1 / world
+        step_kw["world_size"] = ctx.world
     if a["mean_teacher"]:                                                        # ema_model = create_model(ema=True) (:238-251)
         teacher = build_teacher(make).eval()
-        step = ChapStep(model, a, teacher=teacher, **mon_kw)
+        step = ChapStep(model, a, teacher=teacher, **step_kw)
     else:
-        teacher, step = None, ChapStep(model, a, **mon_kw)
+        teacher, step = None, ChapStep(model, a, **step_kw)
+    attach_step(ctx, step, a)                   # (data-parallel) rank 0's weights everywhere, the gradient exchange, the rank's noise stream
     loader = a.get("trainloader")
     if loader is None and a.get("root_path") and a.get("labeled_slices"):
         from .data import DeviceLoader, SliceStore
         store = SliceStore.from_h5_dir(a["root_path"], "train", device)
         n_lab = int(a["labeled_slices"])
-        loader = DeviceLoader(store, range(n_lab), range(n_lab, len(store)), a["batch_size"], a["labeled_bs"], a["image_size"], a["seed"])
-    loader = loader or _synthetic_loader(a)
+        loader = DeviceLoader(store, range(n_lab), range(n_lab, len(store)), a["batch_size"], a["labeled_bs"], a["image_size"], a["seed"],
+                              rank=ctx.rank, world=ctx.world)
+    loader = loader or _synthetic_loader(a, ctx.rank)
     device_fed = a["use_graph"] and hasattr(loader, "next_into")      # the next batch is built on the device, beside the running iteration
     val = a.get("val_volumes")
     if val is None:
@@ -80,8 +112,10 @@ def train(args, snapshot_path):
     best, ema_best, captured = 0.0, -1.0, False         # (the first validated teacher is the best so far, whatever it scores)
 
     def validate(net):
-        metric = sum(np.array(test_single_volume(im, lb, net, classes=a["num_classes"], patch_size=a["image_size"],
-                                                 model_type="logit_ensemble", device=device)) for im, lb in val) / len(val)
+        # each rank scores its shard of the volumes; the sum runs over the gathered values in volume order (one process: over all of them, as ever)
+        per = [np.array(test_single_volume(im, lb, net, classes=a["num_classes"], patch_size=a["image_size"],
+                                           model_type="logit_ensemble", device=device)) for im, lb in ctx.shard(val)]
+        metric = sum(ctx.gather_in_order(per, len(val))) / len(val)
         return float(np.mean(metric, axis=0)[0]), float(np.mean(metric, axis=0)[1])
 
     def batches():
@@ -112,26 +146,32 @@ def train(args, snapshot_path):
         if it % 50 == 0:                                                         # (:404 logs every iteration: a host sync each)
             log.info("iteration %d : bcp loss : %f vat loss : %f" % (it, sum(float(l[2]) for l in out["mix_losses"]), float(out["vat_loss"])))
         if it > 0 and it % a["val_interval"] == 0:                               # :407-456
+            sync_for_validation(ctx, step)       # (data-parallel) replicas equal, else raise; rank 0's BatchNorm statistics into every replica
             model.eval()
             performance, mean_hd95 = validate(model)
-            torch.save(model.state_dict(), os.path.join(snapshot_path, "latest.pth"))
-            if performance > best:
+            if ctx.is_main:
+                torch.save(model.state_dict(), os.path.join(snapshot_path, "latest.pth"))
+            if performance > best:              # the same decision on every rank: `performance` is the same word everywhere
                 best = performance
-                torch.save(model.state_dict(), os.path.join(snapshot_path, "{}_best_model.pth".format(a["model"])))
-                with open(os.path.join(snapshot_path, "val.csv"), "a", newline="") as f:
-                    csv.writer(f).writerow([time.strftime("%Y-%m-%d %H:%M:%S"), it, round(best, 4)])
+                if ctx.is_main:
+                    torch.save(model.state_dict(), os.path.join(snapshot_path, "{}_best_model.pth".format(a["model"])))
+                    with open(os.path.join(snapshot_path, "val.csv"), "a", newline="") as f:
+                        csv.writer(f).writerow([time.strftime("%Y-%m-%d %H:%M:%S"), it, round(best, 4)])
             log.info("iteration %d : model1_mean_dice : %f model1_mean_hd95 : %f" % (it, performance, mean_hd95))      # :453-454
             if teacher is not None:             # the averaged weights with the student's current BatchNorm statistics, after the student, same function
                 step.sync_teacher_stats()
                 ema_dice, ema_hd95 = validate(teacher)
-                torch.save(teacher.state_dict(), os.path.join(snapshot_path, "ema_latest.pth"))
+                if ctx.is_main:
+                    torch.save(teacher.state_dict(), os.path.join(snapshot_path, "ema_latest.pth"))
                 if ema_dice > ema_best:
                     ema_best = ema_dice
-                    torch.save(teacher.state_dict(), os.path.join(snapshot_path, "{}_ema_best_model.pth".format(a["model"])))
+                    if ctx.is_main:
+                        torch.save(teacher.state_dict(), os.path.join(snapshot_path, "{}_ema_best_model.pth".format(a["model"])))
                 log.info("iteration %d : ema_mean_dice : %f ema_mean_hd95 : %f" % (it, ema_dice, ema_hd95))
             model.train()
+            ctx.barrier()                       # no rank runs ahead of a half-written checkpoint
         if mon is not None and (it % a["val_interval"] == 0 or it >= a["max_iterations"]):
-            flush_to_run(mon, snapshot_path, log)
+            flush_monitor(ctx, mon, snapshot_path, log)
         if it >= a["max_iterations"]:
             break
         if device_fed:
@@ -140,6 +180,4 @@ def train(args, snapshot_path):
         sampled_batch = next(gen)
         if a["use_graph"]:
             step.stage(sampled_batch["image"], sampled_batch["label"])      # travels while the iteration enqueued above runs
-    log.removeHandler(fh)
-    fh.close()
     return model

@@ -10,7 +10,12 @@ volumes resident on the device, random crops zero-padded where a volume is small
 generator.  Validation: `args["val_volumes"]`, a list of (image [w,h,d], label [w,h,d]) arrays, scored by the sliding window of
 chap_amd.test_3d_patch.var_all_case (mean foreground Dice, first decoder: binary, whatever `num_classes` (2..8) is -- per-class 3D
 validation is not built).  `dropout=True` is unsupported in 3D (ChapStep raises).
-`args["has_residual"]` (default False) builds the network with residual V-Net blocks (vnet.py:37-67)."""
+`args["has_residual"]` (default False) builds the network with residual V-Net blocks (vnet.py:37-67).
+
+`args["data_parallel"]`: this process is one rank of the run, exactly as in chap_amd/train_ours_2D.py (see there and DESIGN.md section 6
+"train() on several ranks"): per-rank `batch_size` / `labeled_bs`, the rank's shard of the DeviceLoader built here, the fold-schedule gradient
+exchange, validation split over the ranks case by case (var_each_case below, the mean taken over the gathered values in case order),
+files written by rank 0 alone.  The loss line of every 50th iteration is rank 0's LOCAL values."""
 import csv
 import logging
 import os
@@ -19,39 +24,61 @@ import time
 import numpy as np
 import torch
 
-from .monitor import StepMonitor, flush_to_run
+from .distributed import attach_step, flush_monitor, init_rank, sync_for_validation
+from .monitor import StepMonitor
 from .networks.net_factory_3d import net_factory_3d
 from .networks.vnet import DualDecoder3d, VNet
 from .synthetic import synthetic_batch_3d
-from .test_3d_patch import var_all_case
+from . import metrics
+from . import test_3d_patch as T3P
 from .train import DEFAULT_ARGS, ChapStep, build_teacher, check_num_classes
 
 FLAG_DEFAULTS = dict(DEFAULT_ARGS, model="dualdecoder", num_classes=2, patch_size=[112, 112, 80], batch_size=4, labeled_bs=2,
                      stride_xy=18, stride_z=4, val_interval=200, use_graph=True, gpu=0, seed=1337,
-                     mean_teacher=False, ema_decay=0.99, monitor=False)       # as train_ours_2D: --ema_decay (train_ours_2D.py:499), the ema_model of :251
+                     mean_teacher=False, ema_decay=0.99, monitor=False,       # as train_ours_2D: --ema_decay (train_ours_2D.py:499), the ema_model of :251
+                     data_parallel=False, dp_backend="nccl", dp_timeout_s=600, dp_force_group=False, dp_noise_per_rank=True)      # chap_amd.distributed
 
 
-def _synthetic_loader(a):
+def _synthetic_loader(a, rank=0):
     lbs, ubs = a["labeled_bs"], a["batch_size"] - a["labeled_bs"]
-    pool = [synthetic_batch_3d(a["seed"] + i, lbs, ubs, *a["patch_size"], n_classes=a["num_classes"]) for i in range(4)]
+    pool = [synthetic_batch_3d(a["seed"] + 4 * rank + i, lbs, ubs, *a["patch_size"], n_classes=a["num_classes"]) for i in range(4)]      # a pool of its own per data-parallel rank
     while True:
         for v, l in pool:
             yield {"image": v, "label": l}
+
+
+def var_each_case(model, image_list, num_classes, patch_size=(112, 112, 80), stride_xy=18, stride_z=4):
+    """test_3d_patch.var_all_case's per-case foreground Dice values as a list, in the order of `image_list` (which may be empty): the same
+    window, the same counts-only metrics launch per case.  A data-parallel rank scores its shard of the cases with it; the mean is then taken
+    over the gathered values in case order, with var_all_case's arithmetic (0.0 + d0 + d1 + ..., divided by the count)."""
+    device = T3P._model_device(model)
+    out = []
+    for entry in image_list:
+        image, label = T3P._load_case(entry)
+        pred, _ = T3P._predict_device(model, image, stride_xy, stride_z, patch_size, num_classes, T3P.WINDOW_BATCH, device, average=False)
+        with torch.cuda.device(device):
+            out.append(metrics.dc(pred.contiguous(), label))
+    return out
 
 
 def train(args, snapshot_path):
     a = dict(FLAG_DEFAULTS)
     a.update(args)
     check_num_classes(a["num_classes"], "chap_amd.train_ours_3D")
-    os.makedirs(snapshot_path, exist_ok=True)
+    ctx = init_rank(a)                          # the plain single process unless args["data_parallel"]
     log = logging.getLogger("chap_amd.train3d")
     log.setLevel(logging.INFO)
-    fh = logging.FileHandler(os.path.join(snapshot_path, "log.txt"))
-    log.addHandler(fh)
+    fh = None
     try:
-        device = torch.device("cuda", a["gpu"])
+        if ctx.is_main:                         # rank 0 alone writes under snapshot_path
+            os.makedirs(snapshot_path, exist_ok=True)
+            fh = logging.FileHandler(os.path.join(snapshot_path, "log.txt"))
+            log.addHandler(fh)
+        device = ctx.device
+        if ctx.group is not None:
+            torch.cuda.set_device(device)
         torch.manual_seed(a["seed"])
-        np.random.seed(a["seed"])
+        np.random.seed(a["seed"])               # on every rank: ONE BCP box per iteration for the global batch
         def make():
             if a.get("has_residual", False):
                 # ResidualConvBlock nets (vnet.py:37-67): net_factory_3d keeps the reference's signature, which has no such flag, so the class is built
@@ -69,25 +96,37 @@ def train(args, snapshot_path):
             model.set_compute_dtype(torch.bfloat16)
         # monitor: per-iteration pseudo-label quality from inside the step (chap_amd.monitor), read every val_interval iterations
         mon = StepMonitor(a["num_classes"], ring=max(256, int(a["val_interval"])), device=device) if a["monitor"] else None
-        mon_kw = {} if mon is None else {"monitor": mon}
+        step_kw = {} if mon is None else {"monitor": mon}
+        if ctx.group is not None:                   # one replica of several: the fused SGD scales the summed gradient by 1 / world
+            step_kw["world_size"] = ctx.world
         if a["mean_teacher"]:                   # ema_model = create_model(ema=True) (train_ours_2D.py:238-251)
             teacher = build_teacher(make).eval()
-            step = ChapStep(model, a, teacher=teacher, **mon_kw)
+            step = ChapStep(model, a, teacher=teacher, **step_kw)
         else:
-            teacher, step = None, ChapStep(model, a, **mon_kw)
+            teacher, step = None, ChapStep(model, a, **step_kw)
+        attach_step(ctx, step, a)               # (data-parallel) rank 0's weights everywhere, the gradient exchange, the rank's noise stream
         loader = a.get("trainloader")
         if loader is None and a.get("root_path") and a.get("labeled_num"):
             from .data import DeviceLoader, VolumeStore
             store = VolumeStore.from_h5_list(a["root_path"], device=device)
             n_lab = int(a["labeled_num"])
-            loader = DeviceLoader(store, range(n_lab), range(n_lab, len(store)), a["batch_size"], a["labeled_bs"], a["patch_size"], a["seed"], pad=True)
-        loader = loader or _synthetic_loader(a)
+            loader = DeviceLoader(store, range(n_lab), range(n_lab, len(store)), a["batch_size"], a["labeled_bs"], a["patch_size"], a["seed"], pad=True,
+                                  rank=ctx.rank, world=ctx.world)
+        loader = loader or _synthetic_loader(a, ctx.rank)
         device_fed = a["use_graph"] and hasattr(loader, "next_into")      # the next batch is built on the device, beside the running iteration
         val = a.get("val_volumes")
         if val is None:
             vi, vl = synthetic_batch_3d(a["seed"] + 4242, 1, 0, *a["patch_size"], n_classes=a["num_classes"])
             val = [(vi[0, 0].numpy(), vl[0].numpy())]
         best, ema_best, captured = 0.0, -1.0, False         # (the first validated teacher is the best so far, whatever it scores)
+
+        def validate(net):
+            # each rank scores its shard of the cases; the sum runs over the gathered values in case order: var_all_case's arithmetic
+            per = var_each_case(net, ctx.shard(val), a["num_classes"], tuple(a["patch_size"]), a["stride_xy"], a["stride_z"])
+            total = 0.0
+            for d in ctx.gather_in_order(per, len(val)):
+                total += d
+            return float(total / len(val))
 
         def batches():
             """train_ours_2D.py:299-302, 459-463: a finite loader is re-iterated until max_iterations is reached; one that yields nothing ends
@@ -116,26 +155,32 @@ def train(args, snapshot_path):
             if it % 50 == 0:
                 log.info("iteration %d : bcp loss : %f vat loss : %f" % (it, sum(float(l[2]) for l in out["mix_losses"]), float(out["vat_loss"])))
             if it > 0 and it % a["val_interval"] == 0:
+                sync_for_validation(ctx, step)   # (data-parallel) replicas equal, else raise; rank 0's BatchNorm statistics into every replica
                 model.eval()
-                dice = float(var_all_case(model, val, a["num_classes"], tuple(a["patch_size"]), a["stride_xy"], a["stride_z"]))
-                torch.save(model.state_dict(), os.path.join(snapshot_path, "latest.pth"))
-                if dice > best:
+                dice = validate(model)
+                if ctx.is_main:
+                    torch.save(model.state_dict(), os.path.join(snapshot_path, "latest.pth"))
+                if dice > best:                 # the same decision on every rank: `dice` is the same word everywhere
                     best = dice
-                    torch.save(model.state_dict(), os.path.join(snapshot_path, "{}_best_model.pth".format(a["model"])))
-                    with open(os.path.join(snapshot_path, "val.csv"), "a", newline="") as f:
-                        csv.writer(f).writerow([time.strftime("%Y-%m-%d %H:%M:%S"), it, round(best, 4)])
+                    if ctx.is_main:
+                        torch.save(model.state_dict(), os.path.join(snapshot_path, "{}_best_model.pth".format(a["model"])))
+                        with open(os.path.join(snapshot_path, "val.csv"), "a", newline="") as f:
+                            csv.writer(f).writerow([time.strftime("%Y-%m-%d %H:%M:%S"), it, round(best, 4)])
                 log.info("iteration %d : dice_score : %f" % (it, dice))
                 if teacher is not None:         # the averaged weights with the student's current BatchNorm statistics, after the student, same function
                     step.sync_teacher_stats()
-                    ema_dice = float(var_all_case(teacher, val, a["num_classes"], tuple(a["patch_size"]), a["stride_xy"], a["stride_z"]))
-                    torch.save(teacher.state_dict(), os.path.join(snapshot_path, "ema_latest.pth"))
+                    ema_dice = validate(teacher)
+                    if ctx.is_main:
+                        torch.save(teacher.state_dict(), os.path.join(snapshot_path, "ema_latest.pth"))
                     if ema_dice > ema_best:
                         ema_best = ema_dice
-                        torch.save(teacher.state_dict(), os.path.join(snapshot_path, "{}_ema_best_model.pth".format(a["model"])))
+                        if ctx.is_main:
+                            torch.save(teacher.state_dict(), os.path.join(snapshot_path, "{}_ema_best_model.pth".format(a["model"])))
                     log.info("iteration %d : ema_dice_score : %f" % (it, ema_dice))
                 model.train()
+                ctx.barrier()                   # no rank runs ahead of a half-written checkpoint
             if mon is not None and (it % a["val_interval"] == 0 or it >= a["max_iterations"]):
-                flush_to_run(mon, snapshot_path, log)
+                flush_monitor(ctx, mon, snapshot_path, log)
             if it >= a["max_iterations"]:
                 break
             if device_fed:
@@ -144,7 +189,10 @@ def train(args, snapshot_path):
             sampled_batch = next(gen)
             if a["use_graph"]:
                 step.stage(sampled_batch["image"], sampled_batch["label"])      # travels while the iteration enqueued above runs
-    finally:                    # also when the loop raises: a later train() in this process must not log into this file
-        log.removeHandler(fh)
-        fh.close()
+        ctx.barrier()
+    finally:                    # also when the loop raises: leave the process groups; a later train() in this process must not log into this file
+        ctx.close()
+        if fh is not None:
+            log.removeHandler(fh)
+            fh.close()
     return model
