@@ -278,6 +278,26 @@ class SgdEmaParams(C.Structure):
     _fields_ = [("sgd", SgdParams), ("ema", _vp), ("coef", _vp)]
 
 
+class GuardState(C.Structure):
+    _fields_ = [("scale", _f32), ("skip", _i32), ("norm", _f32), ("steps", _i32), ("skipped_total", _i32), ("clipped_total", _i32), ("reserved", _i32 * 2)]
+
+
+class GuardRow(C.Structure):
+    _fields_ = [("step", _i32), ("norm", _f32), ("coef", _f32), ("skip", _i32)]
+
+
+GRADNORM_SLOTS = 512                           # CHAP_GRADNORM_SLOTS of include/chap_hip_guard.h
+
+
+class GradNormParams(C.Structure):
+    _fields_ = [("grad", _vp), ("grad2", _vp), ("n", _i64), ("grad_scale", _f32), ("max_norm", _f32), ("skip_nonfinite", _i32), ("ring", _i32),
+                ("ws", _vp), ("state", _vp)]
+
+
+class SgdGuardParams(C.Structure):
+    _fields_ = [("se", SgdEmaParams), ("state", _vp)]
+
+
 MONITOR_SLOTS, MONITOR_MAX_SCALARS, MONITOR_HDR = 512, 16, 2       # CHAP_MONITOR_* of include/chap_hip_monitor.h
 
 
@@ -318,6 +338,8 @@ _SIGS_EXT = {"chap_sgd_ema_step": SgdEmaParams}
 # the training monitor, declared in include/chap_hip_monitor.h (same calling convention): issued only with a chap_amd.monitor.StepMonitor attached
 _SIGS_MONITOR = {"chap_monitor_accumulate": MonitorParams, "chap_monitor_accumulate_labels": MonitorLabelsParams,
                  "chap_monitor_finalize": MonitorFinalizeParams}
+# the gradient guard, declared in include/chap_hip_guard.h (same calling convention): issued only with a chap_amd.guard.StepGuard attached
+_SIGS_GUARD = {"chap_grad_norm": GradNormParams, "chap_sgd_guard_step": SgdGuardParams}
 _SIZE_FNS = {"chap_pack_size": PackParams, "chap_conv_c1_bwd_ws": ConvC1BwdParams, "chap_wgrad_ws": WgradParams,
              "chap_lcc_ws": LccParams, "chap_metrics_ws": MetricsParams}
 
@@ -368,8 +390,8 @@ def _fn(name):
             fn = getattr(L, name)
         except AttributeError:
             raise ChapError("libchap_hip.so does not export %s (stale build?)" % name)
-        if name in _SIGS or name in _SIGS_EXT or name in _SIGS_MONITOR:
-            fn.restype, fn.argtypes = C.c_int, [C.POINTER(_SIGS.get(name) or _SIGS_EXT.get(name) or _SIGS_MONITOR[name]), _vp]
+        if name in _SIGS or name in _SIGS_EXT or name in _SIGS_MONITOR or name in _SIGS_GUARD:
+            fn.restype, fn.argtypes = C.c_int, [C.POINTER(_SIGS.get(name) or _SIGS_EXT.get(name) or _SIGS_MONITOR.get(name) or _SIGS_GUARD[name]), _vp]
         else:
             fn.restype, fn.argtypes = _sz, [C.POINTER(_SIZE_FNS[name])]
         _bound[name] = fn

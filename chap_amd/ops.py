@@ -584,6 +584,37 @@ def sgd_ema_step(param, grad, mom, lr_dev, momentum, weight_decay, ema, coef_dev
 
 
 # ------------------------------------------------------------------------------------------
+# gradient guard (include/chap_hip_guard.h; chap_amd.guard.StepGuard owns the workspace and the state block)
+def guard_state_words(ring):
+    """int32 words of a state block with `ring` rows: CHAP_GUARD_STATE_BYTES(ring) / 4."""
+    import ctypes
+    return (ctypes.sizeof(L.GuardState) + int(ring) * ctypes.sizeof(L.GuardRow)) // 4
+
+
+def grad_norm(grad, grad2, ws, state, ring, grad_scale=1.0, max_norm=0.0, skip_nonfinite=True):
+    """norm = sqrt(sum (grad + grad2)^2) * grad_scale in a fixed order (fp64), and from it the clip coefficient min(1, max_norm / (norm + 1e-6))
+    (max_norm <= 0: 1) and the skip flag (a non-finite element and `skip_nonfinite`) into `state`: an int32 tensor of guard_state_words(ring)
+    words whose three counters and ring row the launch advances itself.  `ws`: L.GRADNORM_SLOTS fp64 words."""
+    if ws.dtype != torch.float64 or ws.numel() < L.GRADNORM_SLOTS or state.dtype != torch.int32 or state.numel() < guard_state_words(ring):
+        raise ValueError("grad_norm: ws must hold %d fp64 words and state %d int32 words" % (L.GRADNORM_SLOTS, guard_state_words(ring)))
+    p = L.GradNormParams()
+    p.grad, p.grad2, p.n, p.grad_scale, p.max_norm = grad.data_ptr(), _p(grad2), grad.numel(), grad_scale, max_norm
+    p.skip_nonfinite, p.ring, p.ws, p.state = int(bool(skip_nonfinite)), int(ring), ws.data_ptr(), state.data_ptr()
+    L.call("chap_grad_norm", p, _stream())
+
+
+def sgd_guard_step(param, grad, mom, lr_dev, momentum, weight_decay, state, ema=None, coef_dev=None, grad_scale=1.0, zero_grad=True, grad2=None):
+    """sgd_step (ema None) or sgd_ema_step with the gradient scaled by fl32(grad_scale * state.scale), and nothing but the zeroing of the
+    buckets when state.skip is set; `state` as grad_norm left it."""
+    q = L.SgdGuardParams()
+    p = q.se.sgd
+    p.param, p.grad, p.grad2, p.mom, p.lr = param.data_ptr(), grad.data_ptr(), _p(grad2), mom.data_ptr(), lr_dev.data_ptr()
+    p.momentum, p.weight_decay, p.grad_scale, p.n, p.zero_grad = momentum, weight_decay, grad_scale, param.numel(), int(zero_grad)
+    q.se.ema, q.se.coef, q.state = _p(ema), _p(coef_dev), _p(state)
+    L.call("chap_sgd_guard_step", q, _stream())
+
+
+# ------------------------------------------------------------------------------------------
 # training monitor (include/chap_hip_monitor.h; chap_amd.monitor.StepMonitor owns the workspace and the ring)
 def monitor_group_words(C):
     return 8 + 5 * C                    # CHAP_MONITOR_GROUP_WORDS

@@ -72,9 +72,12 @@ class FusedSGD:
 
     `ema` (a flat fp32 tensor of the parameter buffer's size: the mean teacher's parameters): the same launch also averages the weights
     into it, ema = a * ema + b * param (update_ema_variables, :50-54), with (a, b) = `ema_coef`, two fp32 words in device memory that
-    set_ema_step() -- or the owner of the words, ChapStep's schedule block -- fills before every step."""
+    set_ema_step() -- or the owner of the words, ChapStep's schedule block -- fills before every step.
 
-    def __init__(self, model, lr, momentum=0.9, weight_decay=1e-4, ema=None, ema_decay=0.99):
+    `guard` (chap_amd.guard.StepGuard): step() first takes the norm of the gradient it is about to apply (chap_grad_norm) and then issues the
+    guarded form of the same kernel, which reads the clip coefficient and the skip flag from the guard's state block."""
+
+    def __init__(self, model, lr, momentum=0.9, weight_decay=1e-4, ema=None, ema_decay=0.99, guard=None):
         self.model, self.momentum, self.weight_decay = model, momentum, weight_decay
         flat, grad = model.flat_buffers()
         self.mom = torch.zeros_like(flat)
@@ -83,6 +86,16 @@ class FusedSGD:
         self.ema, self.ema_decay, self.ema_coef, self.ema_model = None, float(ema_decay), None, None
         if ema is not None:
             self.set_ema(ema)
+        self.guard = None
+        if guard is not None:
+            self.set_guard(guard)
+
+    def set_guard(self, guard):
+        """None detaches it: step() is the unguarded launch again."""
+        flat = self.model.flat_buffers()[0]
+        if guard is not None and (guard.ws is None or guard.ws.device != flat.device):
+            raise ValueError("chap_amd FusedSGD: the guard lives on %s, the parameters on %s" % (guard.device, flat.device))
+        self.guard = guard
 
     def set_ema(self, ema, model=None):
         """`model`: the module whose parameters are views of `ema` (its packed weight copies go stale with every step)."""
@@ -107,7 +120,12 @@ class FusedSGD:
 
     def step(self, grad_scale=1.0, grad2=None):
         flat, grad = self.model.flat_buffers()
-        if self.ema is None:
+        if self.guard is not None:              # behind the gradient exchange: the norm of what is applied, the same word on every rank
+            self.guard.launch_norm(grad, grad2, grad_scale)
+            ops.sgd_guard_step(flat, grad, self.mom, self.lr_dev, self.momentum, self.weight_decay, self.guard.state, self.ema, self.ema_coef, grad_scale, True, grad2)
+            if self.ema_model is not None:
+                self.ema_model.mark_params_dirty()
+        elif self.ema is None:
             ops.sgd_step(flat, grad, self.mom, self.lr_dev, self.momentum, self.weight_decay, grad_scale, True, grad2)
         else:
             ops.sgd_ema_step(flat, grad, self.mom, self.lr_dev, self.momentum, self.weight_decay, self.ema, self.ema_coef, grad_scale, True, grad2)
@@ -290,7 +308,7 @@ class ChapStep:
 
     MONITOR_LAYOUT = "chap"         # what the scalar words of a monitor row hold (chap_amd.monitor.SCALAR_LAYOUTS)
 
-    def __init__(self, model, args=None, optimizer=None, world_size=1, teacher=None, monitor=None):
+    def __init__(self, model, args=None, optimizer=None, world_size=1, teacher=None, monitor=None, guard=None):
         a = dict(DEFAULT_ARGS)
         a.update(args or {})
         self.args, self.model = a, model
@@ -321,6 +339,11 @@ class ChapStep:
             self.opt.lr_dev = self._sched[7:8].view(torch.float32)
         if teacher is not None:
             self._attach_teacher(teacher)
+        self.guard = guard
+        if guard is not None:
+            if not isinstance(self.opt, FusedSGD):
+                raise ValueError("chap_amd ChapStep: a gradient guard needs the fused optimizer (FusedSGD): clip and skip are part of that kernel")
+            self.opt.set_guard(guard)
         self.iter_num = 0
         self.world_size = world_size
         self.grad_sync = None                   # parallel.DataParallelSync (world_size > 1)
@@ -462,6 +485,8 @@ class ChapStep:
                 "gradsim": None if self.gradsim is None else [sc.detach().clone() for sc in self.gradsim.get_sim()]}
         if self.teacher is not None:
             st["ema"] = self.opt.ema.detach().clone()
+        if self.guard is not None:
+            st["guard"] = self.guard.state_dict()
         return st
 
     def load_state_dict(self, st):
@@ -481,6 +506,8 @@ class ChapStep:
             ema = st.get("ema")
             self.opt.ema.copy_(self.model.flat_buffers()[0] if ema is None else ema)
             self.teacher.mark_params_dirty()
+        if self.guard is not None and st.get("guard") is not None:      # a checkpoint of a run without a guard: the counters stay
+            self.guard.load_state_dict(st["guard"])
         return self
 
     # ------------------------------------------------------------------ the device work
@@ -762,6 +789,7 @@ class ChapStep:
         self._static_l = label_batch.clone()
         snap = self.state_dict() if (restore and warmup > 0) else None
         mon_snap = self.monitor.snapshot() if (snap is not None and self.monitor is not None) else None
+        guard_snap = self.guard.snapshot() if (snap is not None and self.guard is not None) else None
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
@@ -775,6 +803,8 @@ class ChapStep:
             self.load_state_dict(snap)
             if mon_snap is not None:            # the warm-up iterations' rows go with their updates
                 self.monitor.restore(mon_snap)
+            if guard_snap is not None:          # ... and so do the guard's rows and counts
+                self.guard.restore(guard_snap)
             torch.cuda.synchronize()
         self.model._rng.reset_counter()
         np_state = np.random.get_state()

@@ -30,6 +30,7 @@ import torch
 
 from .distributed import attach_step, flush_monitor, init_rank, sync_for_validation
 from .inference import test_single_volume
+from .guard import StepGuard, check_finite_before_save, flush_to_run as flush_guard
 from .monitor import StepMonitor
 from .networks.net_factory import net_factory
 from .synthetic import synthetic_batch
@@ -39,6 +40,7 @@ FLAG_DEFAULTS = dict(DEFAULT_ARGS, model="dualdecoder", decoder_type="mcnet", gp
                      val_interval=200, labeled_num=7, use_graph=True,          # train_ours_2D.py:469-526
                      mean_teacher=False, ema_decay=0.99,                       # --ema_decay (:499); mean_teacher: the commented-out ema_model (:251)
                      monitor=False,                                            # chap_amd.monitor: monitor.csv and the loss line of :404-405
+                     clip_grad_norm=0.0, skip_nonfinite=False,                 # chap_amd.guard: clip by the global gradient norm (0 = off), skip non-finite steps; guard.csv
                      data_parallel=False, dp_backend="nccl", dp_timeout_s=600, dp_force_group=False, dp_noise_per_rank=True)      # chap_amd.distributed
 
 
@@ -88,6 +90,11 @@ def _run(a, snapshot_path, ctx, log):
     # monitor: per-iteration pseudo-label quality from inside the step (chap_amd.monitor), read every val_interval iterations
     mon = StepMonitor(a["num_classes"], ring=max(256, int(a["val_interval"])), device=device) if a["monitor"] else None
     step_kw = {} if mon is None else {"monitor": mon}
+    # guard: clip by the global gradient norm and / or skip non-finite steps inside the optimizer launch (chap_amd.guard), read like the monitor
+    guard = None
+    if float(a["clip_grad_norm"]) > 0 or a["skip_nonfinite"]:
+        guard = StepGuard(max_norm=float(a["clip_grad_norm"]), skip_nonfinite=bool(a["skip_nonfinite"]), ring=max(256, int(a["val_interval"])), device=device)
+        step_kw["guard"] = guard
     if ctx.group is not None:                   # one replica of several: the fused SGD scales the summed gradient by 1 / world
         step_kw["world_size"] = ctx.world
     if a["mean_teacher"]:                                                        # ema_model = create_model(ema=True) (:238-251)
@@ -149,6 +156,8 @@ def _run(a, snapshot_path, ctx, log):
             sync_for_validation(ctx, step)       # (data-parallel) replicas equal, else raise; rank 0's BatchNorm statistics into every replica
             model.eval()
             performance, mean_hd95 = validate(model)
+            # the checkpoint gate, on every rank (the replicas are equal: the same decision everywhere): no file is overwritten with a non-finite model
+            check_finite_before_save(model.state_dict(), "the model", it)
             if ctx.is_main:
                 torch.save(model.state_dict(), os.path.join(snapshot_path, "latest.pth"))
             if performance > best:              # the same decision on every rank: `performance` is the same word everywhere
@@ -161,6 +170,7 @@ def _run(a, snapshot_path, ctx, log):
             if teacher is not None:             # the averaged weights with the student's current BatchNorm statistics, after the student, same function
                 step.sync_teacher_stats()
                 ema_dice, ema_hd95 = validate(teacher)
+                check_finite_before_save(teacher.state_dict(), "the mean teacher", it)
                 if ctx.is_main:
                     torch.save(teacher.state_dict(), os.path.join(snapshot_path, "ema_latest.pth"))
                 if ema_dice > ema_best:
@@ -172,6 +182,8 @@ def _run(a, snapshot_path, ctx, log):
             ctx.barrier()                       # no rank runs ahead of a half-written checkpoint
         if mon is not None and (it % a["val_interval"] == 0 or it >= a["max_iterations"]):
             flush_monitor(ctx, mon, snapshot_path, log)
+        if guard is not None and ctx.is_main and (it % a["val_interval"] == 0 or it >= a["max_iterations"]):
+            flush_guard(guard, snapshot_path, log)       # rank 0 alone: the rows are the same words on every rank
         if it >= a["max_iterations"]:
             break
         if device_fed:

@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from .distributed import attach_step, flush_monitor, init_rank, sync_for_validation
+from .guard import StepGuard, check_finite_before_save, flush_to_run as flush_guard
 from .monitor import StepMonitor
 from .networks.net_factory_3d import net_factory_3d
 from .networks.vnet import DualDecoder3d, VNet
@@ -36,6 +37,7 @@ from .train import DEFAULT_ARGS, ChapStep, build_teacher, check_num_classes
 FLAG_DEFAULTS = dict(DEFAULT_ARGS, model="dualdecoder", num_classes=2, patch_size=[112, 112, 80], batch_size=4, labeled_bs=2,
                      stride_xy=18, stride_z=4, val_interval=200, use_graph=True, gpu=0, seed=1337,
                      mean_teacher=False, ema_decay=0.99, monitor=False,       # as train_ours_2D: --ema_decay (train_ours_2D.py:499), the ema_model of :251
+                     clip_grad_norm=0.0, skip_nonfinite=False,                # chap_amd.guard, as train_ours_2D
                      data_parallel=False, dp_backend="nccl", dp_timeout_s=600, dp_force_group=False, dp_noise_per_rank=True)      # chap_amd.distributed
 
 
@@ -97,6 +99,11 @@ def train(args, snapshot_path):
         # monitor: per-iteration pseudo-label quality from inside the step (chap_amd.monitor), read every val_interval iterations
         mon = StepMonitor(a["num_classes"], ring=max(256, int(a["val_interval"])), device=device) if a["monitor"] else None
         step_kw = {} if mon is None else {"monitor": mon}
+        # guard: clip by the global gradient norm and / or skip non-finite steps inside the optimizer launch (chap_amd.guard), read like the monitor
+        guard = None
+        if float(a["clip_grad_norm"]) > 0 or a["skip_nonfinite"]:
+            guard = StepGuard(max_norm=float(a["clip_grad_norm"]), skip_nonfinite=bool(a["skip_nonfinite"]), ring=max(256, int(a["val_interval"])), device=device)
+            step_kw["guard"] = guard
         if ctx.group is not None:                   # one replica of several: the fused SGD scales the summed gradient by 1 / world
             step_kw["world_size"] = ctx.world
         if a["mean_teacher"]:                   # ema_model = create_model(ema=True) (train_ours_2D.py:238-251)
@@ -158,6 +165,8 @@ def train(args, snapshot_path):
                 sync_for_validation(ctx, step)   # (data-parallel) replicas equal, else raise; rank 0's BatchNorm statistics into every replica
                 model.eval()
                 dice = validate(model)
+                # the checkpoint gate, on every rank (the replicas are equal: the same decision everywhere): no file is overwritten with a non-finite model
+                check_finite_before_save(model.state_dict(), "the model", it)
                 if ctx.is_main:
                     torch.save(model.state_dict(), os.path.join(snapshot_path, "latest.pth"))
                 if dice > best:                 # the same decision on every rank: `dice` is the same word everywhere
@@ -170,6 +179,7 @@ def train(args, snapshot_path):
                 if teacher is not None:         # the averaged weights with the student's current BatchNorm statistics, after the student, same function
                     step.sync_teacher_stats()
                     ema_dice = validate(teacher)
+                    check_finite_before_save(teacher.state_dict(), "the mean teacher", it)
                     if ctx.is_main:
                         torch.save(teacher.state_dict(), os.path.join(snapshot_path, "ema_latest.pth"))
                     if ema_dice > ema_best:
@@ -181,6 +191,8 @@ def train(args, snapshot_path):
                 ctx.barrier()                   # no rank runs ahead of a half-written checkpoint
             if mon is not None and (it % a["val_interval"] == 0 or it >= a["max_iterations"]):
                 flush_monitor(ctx, mon, snapshot_path, log)
+            if guard is not None and ctx.is_main and (it % a["val_interval"] == 0 or it >= a["max_iterations"]):
+                flush_guard(guard, snapshot_path, log)       # rank 0 alone: the rows are the same words on every rank
             if it >= a["max_iterations"]:
                 break
             if device_fed:
