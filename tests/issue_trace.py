@@ -24,6 +24,9 @@ executor's and the training step's schedules were rewritten (tests/test_issue_or
 RichRecorder keeps a second record beside that one, which `text()` and its hashes do not see: every launch with the memory it reads and
 writes, torch's own device work, the host's waits (`python -m tests.issue_trace --rich DIR [case ...]` writes DIR/<case>.rich.txt).
 tests/launch_order.py checks on it that every two launches which meet in memory are ordered (tests/test_launch_order_gpu.py).
+
+OPT_CASES are the same steps with the opt-in features attached (mean teacher, gradient guard, monitor), rich records only; record_interval()
+and record_loader_replays() record what runs between and beside replays (a validation interval with both readers; stage_from(loader)).
 """
 import bisect
 import contextlib
@@ -519,24 +522,68 @@ CASES = {
     "2d_eager_bf16_c1_direct0": dict(net="2d", mode="eager", env={"CHAP_C1_DIRECT": "0"}, bf16=True),
 }
 
+# The same steps with the opt-in features attached: a mean teacher (chap_sgd_ema_step in place of chap_sgd_step), a gradient guard
+# (chap_grad_norm, then chap_sgd_guard_step in its place) and a training monitor (its three launches; AblationStep: two).  NOT part of CASES:
+# these have no record of the first kind in tests/golden/issue_order_parent.txt -- the features did not exist on that commit -- and are
+# checked for order alone (tests/test_launch_order_gpu.py).  Further keys: teacher, guard, monitor (bool), classes (2D: the model's class
+# count; three issues pass B's single-term loss launches, tests/test_class_counts_step_gpu.py).
+_ALL = dict(teacher=True, guard=True, monitor=True)
+OPT_CASES = {
+    "2d_teacher_eager": dict(net="2d", mode="eager", teacher=True),
+    "2d_teacher_captured": dict(net="2d", mode="captured", teacher=True),
+    "2d_guard_eager": dict(net="2d", mode="eager", guard=True),
+    "2d_guard_captured": dict(net="2d", mode="captured", guard=True),
+    "2d_guard_teacher_eager": dict(net="2d", mode="eager", guard=True, teacher=True),
+    "2d_guard_teacher_captured": dict(net="2d", mode="captured", guard=True, teacher=True),
+    "2d_all_eager": dict(net="2d", mode="eager", **_ALL),
+    "2d_all_captured": dict(net="2d", mode="captured", **_ALL),
+    "2d_all_bf16_captured": dict(net="2d", mode="captured", bf16=True, **_ALL),
+    "3d_all_eager": dict(net="3d", mode="eager", **_ALL),
+    "3d_all_captured": dict(net="3d", mode="captured", **_ALL),
+    "3d_residual_all_captured": dict(net="3d_res", mode="captured", **_ALL),
+    "2d_ablation_all_eager": dict(net="2d", mode="eager", step="ablation", **_ALL),
+    "2d_all_c3_captured": dict(net="2d", mode="captured", classes=3, **_ALL),
+}
+# The recorded step must clip, so that the guarded optimizer takes its scaled path (coef < 1): the global gradient norm of these steps is
+# 6 to 150 (2D 12.2, 3D 150.5, ablation 6.5), thousands of times this; tests/test_launch_order_gpu.py asserts 0 < coef < 0.1.
+GUARD_MAX_NORM = 1e-3
+MONITOR_RING = 8
+
+
+def opt_entry_points(case):
+    """{entry point: launches} that the opt-in features of a case add to one iteration, and `absent`: the optimizer entries they replace."""
+    want = {}
+    if case.get("guard"):
+        want.update(chap_grad_norm=1, chap_sgd_guard_step=1)
+    elif case.get("teacher"):
+        want["chap_sgd_ema_step"] = 1
+    if case.get("monitor"):
+        want.update(chap_monitor_accumulate=1, chap_monitor_finalize=1)
+        if case.get("step") != "ablation":          # AblationStep has no largest-component filter: no label-map launch
+            want["chap_monitor_accumulate_labels"] = 1
+    absent = [n for n in ("chap_sgd_step", "chap_sgd_ema_step", "chap_sgd_guard_step", "chap_grad_norm", "chap_monitor_accumulate",
+                          "chap_monitor_accumulate_labels", "chap_monitor_finalize") if n not in want]
+    return want, absent
+
+
 _inputs = {}
 
 
-def _net_inputs(net):
+def _net_inputs(net, classes=None):
     """State, batch, injected randomness and box of tests/test_train_step_gpu.py::test_grouped_decoder_launches_equal_separate_launches
-    (made once per process; nothing here changes them)."""
-    key = "2d" if net == "2d" else "3d"
+    (made once per process; nothing here changes them).  `classes`: a 2D model of another class count than the default four."""
+    key = ("2d" if net == "2d" else "3d") + ("_c%d" % classes if classes else "")
     if key not in _inputs:
         from oracle import init as oinit
         from oracle import train_step as ots
         from tests.iteration_parity import inject_2d, inject_3d, to_dev
-        if key == "2d":
+        if key.startswith("2d"):
             B, lbs, sp = 8, 4, (64, 64)
-            state = oinit.dual_decoder_2d_state(301)
-            vol, lab = ots.synthetic_batch(1337, lbs, B - lbs, *sp)
+            state = oinit.dual_decoder_2d_state(301, n_class=classes) if classes else oinit.dual_decoder_2d_state(301)
+            vol, lab = ots.synthetic_batch(1337, lbs, B - lbs, *sp, classes) if classes else ots.synthetic_batch(1337, lbs, B - lbs, *sp)
             inj = to_dev(inject_2d(B - lbs, lbs // 2 + (B - lbs) // 2, sp[0], sp[1], 2), 2)
             inj["drop_F"] = to_dev({"drop_F": oinit.drop_masks_2d(11, B, sp[0], sp[1])}, 2)["drop_F"]      # AblationStep's full-batch pass
-            box, extra = (7, 11), {}
+            box, extra = (7, 11), ({"num_classes": classes} if classes else {})
         else:
             B, lbs, sp = 4, 2, (16, 32, 16)
             state = oinit.dual_decoder_3d_state(401)
@@ -561,12 +608,13 @@ def _environ(env):
                 os.environ[k] = v
 
 
-def _pack_entries_of(model):
-    """device pointer of a chap_pack_multi table -> the host-side PackEntry array the executor built it from"""
+def _pack_entries_of(*models):
+    """device pointer of a chap_pack_multi table -> the host-side PackEntry array the executor (of one of `models`) built it from"""
     def find(ptr):
-        for tab in model._exec._packed.values():
-            if tab["table"].data_ptr() == int(ptr):
-                return tab["entries"]
+        for model in models:
+            for tab in model._exec._packed.values():
+                if tab["table"].data_ptr() == int(ptr):
+                    return tab["entries"]
         return None
     return find
 
@@ -575,31 +623,52 @@ def _case_step(name):
     """(step, inputs, injected randomness, environment) of one case: the model with the case's state, its training step not yet run."""
     from chap_amd.networks import DualDecoder, DualDecoder3d
     from chap_amd.train import AblationStep, ChapStep
-    case = CASES[name]
-    inp = _net_inputs(case["net"])
-    if case["net"] == "2d":
-        m = DualDecoder(1, 4, {"decoder_type": "mcnet"})
-    else:
-        m = DualDecoder3d(n_channels=1, n_classes=2, normalization="batchnorm", has_dropout=True, has_residual=case["net"] == "3d_res")
-    m = m.to(DEV).train()
+    case = _case(name)
+    inp = _net_inputs(case["net"], case.get("classes"))
+    classes = case.get("classes") or (4 if case["net"] == "2d" else 2)
+
+    def make():
+        if case["net"] == "2d":
+            return DualDecoder(1, classes, {"decoder_type": "mcnet"})
+        return DualDecoder3d(n_channels=1, n_classes=classes, normalization="batchnorm", has_dropout=True, has_residual=case["net"] == "3d_res")
+
+    m = make().to(DEV).train()
     m.load_state_dict(inp["state"], strict=True)
     if case.get("bf16"):
         m.set_compute_dtype(torch.bfloat16)
+    features, extra_args = {}, {}
+    if case.get("teacher"):         # as tests/test_mean_teacher_step_gpu.py builds it: weights of its own, of which nothing survives the first step
+        from chap_amd.train import build_teacher
+
+        def make_teacher():
+            torch.manual_seed(99)
+            return make().to(DEV)
+        features["teacher"], extra_args["ema_decay"] = build_teacher(make_teacher).eval(), 0.99
+    if case.get("guard"):
+        from chap_amd.guard import StepGuard
+        features["guard"] = StepGuard(max_norm=GUARD_MAX_NORM, skip_nonfinite=True, device=DEV)
+    if case.get("monitor"):
+        from chap_amd.monitor import StepMonitor
+        features["monitor"] = StepMonitor(classes, ring=MONITOR_RING, device=DEV)
     inj = dict(inp["inj"])
     if case.get("fp_inject"):       # no host copies under capture: the scripted draws of the perturbed pass on the device (tests/test_train_step_gpu.py:262-278)
         from oracle import filter_dropout as ofd
         _, scores, uniforms = ofd.fd_inputs(B=inp["vol"].shape[0] - inp["args"]["labeled_bs"])
         inj.update(fp_uniforms=[(a.to(DEV), b.to(DEV)) for a, b in uniforms], sim_score=[sc.to(DEV) for sc in scores])
     with _environ(case.get("env", {})):
-        step = (AblationStep if case.get("step") == "ablation" else ChapStep)(m, dict(inp["args"], **case.get("args", {})))
+        step = (AblationStep if case.get("step") == "ablation" else ChapStep)(m, dict(inp["args"], **extra_args, **case.get("args", {})), **features)
     step.iter_num = 4500
     return step, inp, inj
 
 
+def _case(name):
+    return CASES[name] if name in CASES else OPT_CASES[name]
+
+
 def record_case(name, rich=False, exact=False):
-    """Run one case on the GPU and return its full text record; with `rich`, (that record, the rich record) of a RichRecorder (`exact`:
-    with the allocator's snapshot read after every allocation and free, _Allocations)."""
-    case = CASES[name]
+    """Run one case (of CASES or OPT_CASES) on the GPU and return its full text record; with `rich`, (that record, the rich record) of a
+    RichRecorder (`exact`: with the allocator's snapshot read after every allocation and free, _Allocations)."""
+    case = _case(name)
     step, inp, inj = _case_step(name)
     with _environ(case.get("env", {})):
         only = case["mode"] == "captured"
@@ -634,6 +703,92 @@ def record_staged_replays():
     return cap.rich_text(), rec.rich_text()
 
 
+def _capture_for_replays(name):
+    """(step, inputs, recorder of the capture, recorder for what follows it) of a captured case: the second recorder shares the first one's
+    allocation map and writes every replay as one GR line with the union of the capture's accesses."""
+    step, inp, inj = _case_step(name)
+    models = [m for m in (step.model, step.teacher) if m is not None]
+    cap = RichRecorder(True, pack_entries=_pack_entries_of(*models))
+    with cap.recording():
+        step.capture(inp["vol"], inp["lab"], warmup=1, inject=inj)
+    torch.cuda.synchronize()
+    rec = RichRecorder(False, allocations=cap.allocs, pack_entries=cap.pack_entries, replay_accesses=union_accesses(cap.rich_text()))
+    return step, inp, cap, rec
+
+
+INTERVAL = "2d_all_interval"                    # not in CASES or OPT_CASES: records of what runs between and around replays
+
+
+def record_interval():
+    """The rich record of what train() does around a validation interval (train_ours_2D.py, the loop behind `it % val_interval == 0`) with
+    teacher, guard and monitor attached: two replays fed by stage(); then the student evaluated on one 64 x 64 slice, sync_teacher_stats()
+    and the teacher evaluated on it -- both read buffers that the captured optimizer launch writes --, StepMonitor.read() and
+    StepGuard.read(), each a copy on a stream of its own between two events; then stage() and a third replay, which writes what the
+    readers copied.  Returns (record of the capture, record of the replays and the interval)."""
+    step, inp, cap, rec = _capture_for_replays("2d_all_captured")
+    model, teacher = step.model, step.teacher
+    x = inp["vol"][:1].contiguous()
+    with rec.recording():
+        for _ in range(2):
+            step.stage(inp["vol"], inp["lab"])
+            step.replay(box_yx=inp["box"])
+        with torch.no_grad():
+            model.eval()
+            model(x)
+            step.sync_teacher_stats()
+            teacher(x)
+            model.train()
+        step.monitor.read()
+        step.guard.read()
+        step.stage(inp["vol"], inp["lab"])
+        step.replay(box_yx=inp["box"])
+    torch.cuda.synchronize()
+    return cap.rich_text(), rec.rich_text()
+
+
+LOADER_REPLAYS = {"2d_loader_double_replay": "2d_captured", "3d_padded_loader_double_replay": "3d_captured"}
+
+
+def _synthetic_loader(net):
+    """A DeviceLoader over a synthetic store of mixed shapes, as tests/test_augment_gpu.py and tests/test_la_kernels_gpu.py build them (2D:
+    twenty slices, some smaller than the output; 3D: six volumes, three of them smaller than some crop, pad=True).  Labels stay inside
+    the networks' class counts: these batches are trained on."""
+    import numpy as np
+    from chap_amd.data import DeviceLoader, SliceStore, VolumeStore
+    rng = np.random.default_rng(5)
+    if net == "2d":
+        shapes = [((256, 216), (216, 256), (224, 154), (37, 29), (96, 88), (80, 72))[i % 6] for i in range(20)]
+        store = SliceStore([rng.random(s, dtype=np.float32) + 0.5 for s in shapes], [rng.integers(0, 4, s).astype(np.uint8) for s in shapes], DEV)
+        return DeviceLoader(store, range(8), range(8, 20), 8, 4, (64, 64), seed=5)
+    shapes = [(20, 30, 12), (40, 40, 36), (24, 24, 24), (10, 50, 30), (44, 44, 44), (33, 35, 31)]
+    store = VolumeStore([rng.random(s, dtype=np.float32) + 0.5 for s in shapes], [rng.integers(0, 2, s).astype(np.uint8) for s in shapes], DEV)
+    return DeviceLoader(store, range(3), range(3, 6), 4, 2, (16, 32, 16), seed=1, pad=True)
+
+
+def record_loader_replays(name):
+    """The rich record of capture, stage_from(loader), replay, stage_from(loader), replay (ChapStep.stage_from: the loader's augmentation
+    kernel fills the staging buffers on the copy stream, beside the running iteration).  Returns (record of the capture, record of the rest)."""
+    step, inp, cap, rec = _capture_for_replays(LOADER_REPLAYS[name])
+    loader = _synthetic_loader("2d" if name.startswith("2d") else "3d")
+    torch.cuda.synchronize()                    # the store's upload is not part of the record
+    with rec.recording():
+        for _ in range(2):
+            step.stage_from(loader)
+            step.replay(box_yx=inp["box"])
+    torch.cuda.synchronize()
+    return cap.rich_text(), rec.rich_text()
+
+
+BETWEEN_REPLAYS = [STAGED_REPLAY, INTERVAL] + list(LOADER_REPLAYS)
+
+
+def record_between_replays(name):
+    """The rich record of one of BETWEEN_REPLAYS (the part behind the capture)."""
+    if name == STAGED_REPLAY:
+        return record_staged_replays()[1]
+    return record_interval()[1] if name == INTERVAL else record_loader_replays(name)[1]
+
+
 def write_records(directory, names=None):
     """Every case's full record to `directory`/<case>.txt and the fixture lines to `directory`/summary.txt (returned)."""
     os.makedirs(directory, exist_ok=True)
@@ -658,12 +813,12 @@ def write_rich_records(directory, names=None):
     os.makedirs(directory, exist_ok=True)
     record_case("2d_eager"), record_case("3d_eager")
     times = []
-    for name in names or list(CASES) + [STAGED_REPLAY]:
+    for name in names or list(CASES) + [STAGED_REPLAY]:         # (the opt-in cases and the other records between replays: by name)
         t0 = time.time()
-        if name != STAGED_REPLAY:
+        if name not in BETWEEN_REPLAYS:
             record_case(name)
         t1 = time.time()
-        rich = record_staged_replays()[1] if name == STAGED_REPLAY else record_case(name, rich=True)[1]
+        rich = record_between_replays(name) if name in BETWEEN_REPLAYS else record_case(name, rich=True)[1]
         t2 = time.time()
         with open(os.path.join(directory, name + ".rich.txt"), "w") as f:
             f.write(rich)

@@ -1,4 +1,5 @@
-"""Access table of the C ABI (include/chap_hip.h): for every entry point of chap_amd._lib._SIGS, and for chap_pack_multi, which pointer
+"""Access table of the C ABI (include/chap_hip.h and the opt-in headers chap_hip_ext.h, chap_hip_monitor.h, chap_hip_guard.h): for every
+entry point of chap_amd._lib's binding tables (_SIGS, _SIGS_EXT, _SIGS_MONITOR, _SIGS_GUARD), and for chap_pack_multi, which pointer
 fields of its params struct a launch reads (R), writes (W) or reads and writes (RW: accumulated outputs, workspaces), and the bytes behind
 each pointer.  Host only: ctypes structs in, plain tuples out.  tests/issue_trace.py resolves every recorded launch through accesses();
 tests/launch_order.py decides from the result which launches conflict.
@@ -34,6 +35,8 @@ _MIX = dict(logits=R, target_a=R, target_b=R, mask=R, acc=RW, loss=RW, dlogits=R
 _MIX_MULTI = {"term." + k: v for k, v in _MIX.items()}
 _AUG = dict(images=R, labels=R, records=R, image_out=W, label_out=W)
 _WINDOW_ACC = dict(logits=R, origins=R, score=RW, cnt=RW)
+_SGD = dict(param=RW, grad=RW, grad2=RW, mom=RW, lr=R)
+_SGD_EMA = dict({"sgd." + k: v for k, v in _SGD.items()}, ema=RW, coef=R)
 
 MODES = {
     "chap_conv_fwd": _CONV,
@@ -69,7 +72,7 @@ MODES = {
     "chap_box_mask": dict(mask=W, box=R),
     "chap_largest_cc": dict(labels=R, out=W, ws=RW),
     "chap_diff_mask": dict(p1=R, p2=R, knowledge=R, out=W, pooled_ws=RW),
-    "chap_sgd_step": dict(param=RW, grad=RW, grad2=RW, mom=RW, lr=R),
+    "chap_sgd_step": _SGD,
     "chap_sample_channel_sum": dict(_src("r"), partial=W),
     "chap_channel_drop": dict(pool_partial=R, grad_sim=R, u1=R, u2=R, mul1=W, mul2=W, probs_out=W),
     "chap_fold_perturbed": dict(g=R, mul=R, out=W),
@@ -84,11 +87,24 @@ MODES = {
     "chap_residual_fwd": dict(_src("r"), **_src("src"), xin=R, out=W),
     "chap_residual_bwd": dict(g=R, out=R, chan_mul=R, gout=W, dxin=W),
     "chap_grad_sum": dict(g=R, out=W),
+    # the opt-in entry points (_SIGS_EXT, _SIGS_GUARD, _SIGS_MONITOR): issued only with a teacher, a StepGuard, a StepMonitor attached
+    "chap_sgd_ema_step": _SGD_EMA,
+    "chap_grad_norm": dict(grad=R, grad2=R, ws=RW, state=RW),           # state: reads `steps`, writes the header and one row
+    "chap_sgd_guard_step": dict({"se." + k: v for k, v in _SGD_EMA.items()}, state=R),
+    # each accumulate launch writes a region of its own of the workspace (partial rows, nothing to zero), which is what lets the two run on two streams
+    "chap_monitor_accumulate": dict(logits=R, labels=R, ws=W),
+    "chap_monitor_accumulate_labels": dict(maps=R, labels=R, ws=W),
+    "chap_monitor_finalize": dict(ws=R, ring=W, slot_iter=R, scalars=R),
 }
 
 
 def struct_of(name):
-    return L.PackEntry if name == "chap_pack_multi" else L._SIGS[name]
+    if name == "chap_pack_multi":
+        return L.PackEntry
+    for table in (L._SIGS, L._SIGS_EXT, L._SIGS_MONITOR, L._SIGS_GUARD):
+        if name in table:
+            return table[name]
+    raise KeyError(name)
 
 
 # ---------------------------------------------------------------------------------------------------------------- struct reflection
@@ -418,9 +434,58 @@ def _diff_mask(p):
             "pooled_ws": span(p.pooled_ws, (p.N * (p.H // p.scale) * (p.W // p.scale) + p.N) * 4)}
 
 
-def _sgd(p):
-    out = {k: span(getattr(p, k), p.n * 4) for k in ("param", "grad", "grad2", "mom")}
-    out["lr"] = span(p.lr, 4)
+def _sgd(p, prefix=""):
+    out = {prefix + k: span(getattr(p, k), p.n * 4) for k in ("param", "grad", "grad2", "mom")}
+    out[prefix + "lr"] = span(p.lr, 4)
+    return out
+
+
+def _sgd_ema(q, prefix=""):
+    """chap_sgd_ema_params: the nested chap_sgd_params, the average [n] and its two coefficients (fp32 a, b)."""
+    out = _sgd(q.sgd, prefix + "sgd.")
+    out[prefix + "ema"], out[prefix + "coef"] = span(q.ema, q.sgd.n * 4), span(q.coef, 8)
+    return out
+
+
+def _grad_norm(p):
+    return {"grad": span(p.grad, p.n * 4), "grad2": span(p.grad2, p.n * 4), "ws": span(p.ws, L.GRADNORM_SLOTS * 8),
+            "state": span(p.state, C.sizeof(L.GuardState) + p.ring * C.sizeof(L.GuardRow))}         # CHAP_GUARD_STATE_BYTES(ring)
+
+
+def _sgd_guard(p):
+    out = _sgd_ema(p.se, "se.")
+    out["state"] = span(p.state, C.sizeof(L.GuardState))        # scale and skip: the header alone, never a row
+    return out
+
+
+# the 8-byte words of the monitor's workspace and ring (the CHAP_MONITOR_* macros of include/chap_hip_monitor.h)
+def _mon_label_region(Cc):
+    return L.MONITOR_HDR + 2 * L.MONITOR_SLOTS * (8 + 5 * Cc)
+
+
+def _mon_ws_words(Cc):
+    return _mon_label_region(Cc) + L.MONITOR_HDR + 2 * L.MONITOR_SLOTS * 4 * Cc
+
+
+def _mon_row_words(Cc):
+    return 1 + 2 * (8 + 5 * Cc) + 2 * 4 * Cc + L.MONITOR_MAX_SCALARS
+
+
+def _mon_accumulate(p):
+    px = p.N * p.P
+    return {"logits[0]": span(p.logits[0], px * p.C * 4), "logits[1]": span(p.logits[1], px * p.C * 4), "labels": span(p.labels, px * 8),
+            "ws": span(p.ws, _mon_label_region(p.C) * 8)}                   # the logits region only
+
+
+def _mon_accumulate_labels(p):
+    px, lr = p.N * p.P, _mon_label_region(p.C)
+    return {"maps[0]": span(p.maps[0], px * 8), "maps[1]": span(p.maps[1], px * 8), "labels": span(p.labels, px * 8),
+            "ws": span((p.ws or 0) + lr * 8, (_mon_ws_words(p.C) - lr) * 8)}    # the label-map region only
+
+
+def _mon_finalize(p):
+    out = {"ws": span(p.ws, _mon_ws_words(p.C) * 8), "ring": span(p.ring, p.ring_rows * _mon_row_words(p.C) * 8), "slot_iter": span(p.slot_iter, 8)}
+    out.update({"scalars[%d]" % k: span(p.scalars[k], 4) for k in range(p.nscalars)})
     return out
 
 
@@ -483,6 +548,8 @@ RULES = {
     "chap_sgd_step": _sgd, "chap_sample_channel_sum": _sample_chansum, "chap_channel_drop": _channel_drop,
     "chap_fold_perturbed": _fold, "chap_grad_sim": _grad_sim,
     "chap_residual_fwd": _residual, "chap_residual_bwd": _residual_bwd, "chap_grad_sum": _grad_sum,
+    "chap_sgd_ema_step": _sgd_ema, "chap_grad_norm": _grad_norm, "chap_sgd_guard_step": _sgd_guard,
+    "chap_monitor_accumulate": _mon_accumulate, "chap_monitor_accumulate_labels": _mon_accumulate_labels, "chap_monitor_finalize": _mon_finalize,
 }
 
 

@@ -8,7 +8,10 @@ import pytest
 from chap_amd import _lib as L
 from tests import launch_access as A
 
-ENTRY_POINTS = list(L._SIGS) + ["chap_pack_multi"]
+# every binding table of chap_amd._lib, found by name: a fifth `_SIGS...` table is walked without anybody remembering to add it here
+SIG_TABLES = {attr: getattr(L, attr) for attr in sorted(vars(L)) if attr.startswith("_SIGS")}
+LAUNCHED = [name for table in SIG_TABLES.values() for name in table]
+ENTRY_POINTS = LAUNCHED + ["chap_pack_multi"]
 
 
 def _bytes(*ranges):
@@ -49,17 +52,38 @@ def test_every_pointer_field_is_classified(name):
     assert set(A.pointer_paths(A.struct_of(name))) == fields
 
 
+def test_the_binding_tables_are_the_four_known_ones_and_disjoint():
+    assert set(SIG_TABLES) >= {"_SIGS", "_SIGS_EXT", "_SIGS_MONITOR", "_SIGS_GUARD"}
+    assert len(LAUNCHED) == len(set(LAUNCHED)) and all(isinstance(t, dict) and t for t in SIG_TABLES.values())
+    for name in ("chap_sgd_ema_step", "chap_grad_norm", "chap_sgd_guard_step", "chap_monitor_accumulate", "chap_monitor_accumulate_labels",
+                 "chap_monitor_finalize"):
+        assert name in ENTRY_POINTS and name not in L._SIGS, name
+
+
 def test_no_classification_or_rule_for_an_unknown_entry_point():
     assert set(A.MODES) == set(ENTRY_POINTS)
-    assert set(A.RULES) <= set(L._SIGS)
+    assert set(A.RULES) <= set(LAUNCHED)
+    for name in LAUNCHED:
+        assert A.struct_of(name) is next(t[name] for t in SIG_TABLES.values() if name in t)
+    with pytest.raises(KeyError):
+        A.struct_of("chap_no_such_entry")
 
 
 def test_accumulated_outputs_and_workspaces_are_read_write():
     for name, field in (("chap_wgrad", "dw"), ("chap_wgrad", "db"), ("chap_wgrad", "ws"), ("chap_conv_c1_bwd", "dw"), ("chap_conv_c1_bwd", "db"),
                         ("chap_act_bwd_reduce", "dgamma"), ("chap_act_bwd_reduce", "dbeta"), ("chap_act_bwd_reduce", "sums"),
                         ("chap_mix_loss_bwd", "dlogits"), ("chap_mix_loss_fwd", "acc"), ("chap_kl_fwd_bwd", "loss"), ("chap_channel_sum", "out"),
-                        ("chap_sgd_step", "param"), ("chap_sgd_step", "grad"), ("chap_bn_finalize", "running_mean"), ("chap_largest_cc", "ws")):
+                        ("chap_sgd_step", "param"), ("chap_sgd_step", "grad"), ("chap_bn_finalize", "running_mean"), ("chap_largest_cc", "ws"),
+                        ("chap_sgd_ema_step", "sgd.param"), ("chap_sgd_ema_step", "sgd.grad"), ("chap_sgd_ema_step", "sgd.grad2"),
+                        ("chap_sgd_ema_step", "sgd.mom"), ("chap_sgd_ema_step", "ema"),
+                        ("chap_sgd_guard_step", "se.sgd.param"), ("chap_sgd_guard_step", "se.sgd.grad"), ("chap_sgd_guard_step", "se.sgd.grad2"),
+                        ("chap_sgd_guard_step", "se.sgd.mom"), ("chap_sgd_guard_step", "se.ema"),
+                        ("chap_grad_norm", "ws"), ("chap_grad_norm", "state")):
         assert A.MODES[name][field] == A.RW, (name, field)
+    # what the optimizer launches only read: the schedule words and the guard's verdict
+    for name, field in (("chap_sgd_ema_step", "sgd.lr"), ("chap_sgd_ema_step", "coef"), ("chap_sgd_guard_step", "se.sgd.lr"),
+                        ("chap_sgd_guard_step", "se.coef"), ("chap_sgd_guard_step", "state"), ("chap_grad_norm", "grad"), ("chap_grad_norm", "grad2")):
+        assert A.MODES[name][field] == A.R, (name, field)
 
 
 def test_null_pointers_give_no_access_and_a_field_without_rule_gives_none():
@@ -410,6 +434,84 @@ def test_diff_mask_sgd_channel_drop_and_grad_sim():
     g = L.GradSimParams()
     g.gl, g.gu, g.score, g.C, g.K = 1000, 2000, 3000, 3, 5
     _spans(_by_field("chap_grad_sim", g), gl=("R", 1000, 60), gu=("R", 2000, 60), score=("RW", 3000, 12))
+
+
+# ---------------------------------------------------------------------------------------------------------------- the opt-in entry points
+def _sgd_fields(s, n):
+    s.param, s.grad, s.grad2, s.mom, s.lr, s.n = 1000, 2000, 3000, 4000, 5000, n
+
+
+def test_mean_teacher_optimizer():
+    q = L.SgdEmaParams()
+    _sgd_fields(q.sgd, 10)
+    q.ema, q.coef = 6000, 7000
+    _spans(_by_field("chap_sgd_ema_step", q), sgd__param=("RW", 1000, 40), sgd__grad=("RW", 2000, 40), sgd__grad2=("RW", 3000, 40),
+           sgd__mom=("RW", 4000, 40), sgd__lr=("R", 5000, 4), ema=("RW", 6000, 40), coef=("R", 7000, 8))        # coef: two fp32 words, a and b
+    q.sgd.grad2 = None
+    assert "sgd.grad2" not in _by_field("chap_sgd_ema_step", q) and len(_by_field("chap_sgd_ema_step", q)) == 6
+
+
+def test_gradient_guard_norm_and_guarded_optimizer():
+    g = L.GradNormParams()
+    g.grad, g.grad2, g.ws, g.state, g.n, g.ring = 2000, 3000, 20000, 9000, 10, 3      # the two buckets of _sgd_fields
+    # 512 fp64 partials; the state block: a header of 8 int32 words, then 3 rows of 4 words
+    _spans(_by_field("chap_grad_norm", g), grad=("R", 2000, 40), grad2=("R", 3000, 40), ws=("RW", 20000, 512 * 8), state=("RW", 9000, 32 + 3 * 16))
+    assert C.sizeof(L.GuardState) == 32 and C.sizeof(L.GuardRow) == 16 and L.GRADNORM_SLOTS == 512
+    q = L.SgdGuardParams()
+    _sgd_fields(q.se.sgd, 10)
+    q.se.ema, q.se.coef, q.state = 6000, 7000, 9000
+    _spans(_by_field("chap_sgd_guard_step", q), se__sgd__param=("RW", 1000, 40), se__sgd__grad=("RW", 2000, 40), se__sgd__grad2=("RW", 3000, 40),
+           se__sgd__mom=("RW", 4000, 40), se__sgd__lr=("R", 5000, 4), se__ema=("RW", 6000, 40), se__coef=("R", 7000, 8),
+           state=("R", 9000, 32))                                                   # the header alone: scale and skip, never a row
+    q.se.ema, q.se.coef = None, None                                                # without a teacher: chap_sgd_step's fields and the state
+    assert sorted(_by_field("chap_sgd_guard_step", q)) == ["se.sgd.grad", "se.sgd.grad2", "se.sgd.lr", "se.sgd.mom", "se.sgd.param", "state"]
+    # the norm launch rewrites what the guarded optimizer reads, and both touch the buckets
+    norm, opt = _by_field("chap_grad_norm", g), _by_field("chap_sgd_guard_step", q)
+    assert A.intersects(norm["state"][1], opt["state"][1]) and A.intersects(norm["grad"][1], opt["se.sgd.grad"][1])
+
+
+def _monitor_params():
+    """C = 2: a group row is 8 + 5 * 2 = 18 words, a label-map row 4 * 2 = 8 words, 512 partial rows per group and two groups; the logits region is
+    2 + 1024 * 18 = 18434 words, the label-map region 2 + 1024 * 8 = 8194 words behind it; a ring row is 1 + 2 * 18 + 2 * 8 + 16 = 69 words."""
+    a = L.MonitorParams()
+    a.logits[0], a.logits[1], a.labels, a.ws, a.N, a.C, a.P = 1000, 2000, 3000, 100000, 2, 2, 5
+    b = L.MonitorLabelsParams()
+    b.maps[0], b.maps[1], b.labels, b.ws, b.N, b.C, b.P = 4000, 5000, 3000, 100000, 2, 2, 5
+    f = L.MonitorFinalizeParams()
+    f.ws, f.ring, f.slot_iter, f.C, f.ring_rows, f.nscalars = 100000, 400000, 6000, 2, 3, 2
+    f.scalars[0], f.scalars[1], f.scalars[2] = 7000, 7004, 7008                     # nscalars = 2: the third pointer is not read
+    return a, b, f
+
+
+def test_monitor_accumulate_launches_and_finalize():
+    a, b, f = _monitor_params()
+    assert (L.MONITOR_HDR, L.MONITOR_SLOTS, L.MONITOR_MAX_SCALARS) == (2, 512, 16)
+    acc = _by_field("chap_monitor_accumulate", a)
+    _spans(acc, labels=("R", 3000, 2 * 5 * 8), ws=("W", 100000, 18434 * 8))
+    assert acc["logits[0]"] == ("R", (1000, 0, 2 * 2 * 5 * 4, 1)) and acc["logits[1]"] == ("R", (2000, 0, 80, 1))
+    lab = _by_field("chap_monitor_accumulate_labels", b)
+    _spans(lab, labels=("R", 3000, 80), ws=("W", 100000 + 18434 * 8, 8194 * 8))
+    assert lab["maps[0]"] == ("R", (4000, 0, 80, 1)) and lab["maps[1]"] == ("R", (5000, 0, 80, 1))
+    fin = _by_field("chap_monitor_finalize", f)
+    _spans(fin, ws=("R", 100000, (18434 + 8194) * 8), ring=("W", 400000, 3 * 69 * 8), slot_iter=("R", 6000, 8))
+    assert fin["scalars[0]"] == ("R", (7000, 0, 4, 1)) and fin["scalars[1]"] == ("R", (7004, 0, 4, 1))
+    assert fin["scalars[2]"] == ("R", None)                                         # beyond nscalars: no rule, and the step never sets it
+    assert sorted(k for k in fin if k.startswith("scalars")) == ["scalars[0]", "scalars[1]", "scalars[2]"]
+
+
+def test_the_two_monitor_accumulate_launches_share_a_workspace_without_meeting():
+    """One `ws` pointer, two regions: the launches may run on two streams (ChapStep issues the label-map one on pass B's stream), and the
+    finalize launch, which reads both regions, needs an order against each."""
+    a, b, f = _monitor_params()
+    acc, lab, fin = (_by_field(n, p)["ws"][1] for n, p in (("chap_monitor_accumulate", a), ("chap_monitor_accumulate_labels", b), ("chap_monitor_finalize", f)))
+    assert a.ws == b.ws == f.ws
+    assert not A.intersects(acc, lab) and A.bounds(acc)[1] == A.bounds(lab)[0]       # back to back: no gap, no shared byte
+    assert A.intersects(acc, fin) and A.intersects(lab, fin)
+    assert A.bounds(fin) == (A.bounds(acc)[0], A.bounds(lab)[1])
+    for Cc in range(2, 9):                                                          # every class count the kernels are built for
+        a.C = b.C = f.C = Cc
+        acc, lab, fin = (_by_field(n, p)["ws"][1] for n, p in (("chap_monitor_accumulate", a), ("chap_monitor_accumulate_labels", b), ("chap_monitor_finalize", f)))
+        assert not A.intersects(acc, lab) and A.intersects(acc, fin) and A.intersects(lab, fin), Cc
 
 
 def test_every_rule_has_a_case_in_this_file():

@@ -1,7 +1,9 @@
 """The happens-before check of tests/launch_order.py on small hand-written records, one per rule, and on the committed rich record of the
 captured 2D step (tests/golden/launch_order_2d_captured.txt.gz, this project's own output: `python -m tests.issue_trace --rich DIR
 2d_captured`): every stream wait of that record is taken out in turn -- on the record, never on the device -- and the check has to notice
-the joins the iteration depends on."""
+the joins the iteration depends on.  The same on the records with the opt-in features (launch_order_2d_all_captured.txt.gz: teacher, guard
+and monitor attached; launch_order_2d_all_interval.txt.gz: three replays with a validation interval and both readers between them,
+`python -m tests.issue_trace --rich DIR 2d_all_captured 2d_all_interval`): the joins the opt-in launches hang on, and the readers' two waits."""
 import gzip
 import os
 
@@ -153,7 +155,171 @@ def test_two_lanes_accumulating_into_one_dw_are_flagged():
     assert analyze(lanes(0x10000 + 16 * 16 * 9 * 4)) == []           # the next layer's slice of the flat gradient buffer
 
 
-# ---------------------------------------------------------------------------------------------------------------- the committed record
+def _grad_norm(grad, ws, state, ring=4):
+    p = L.GradNormParams()
+    p.grad, p.n, p.ring, p.ws, p.state = grad, 256, ring, ws, state
+    return p
+
+
+def test_the_guards_state_block_is_written_by_the_norm_launch(monkeypatch):
+    """chap_grad_norm on one stream, StepGuard's copy of the state block on another, no join: a finding -- and only because the table says
+    that the launch WRITES the block.  With `state` declared R the same record is clean: the mode carries the finding, not the analyser."""
+    assert launch_access.MODES["chap_grad_norm"]["state"] == "RW"
+    state, nbytes = 0x9000, 32 + 4 * 16
+    copy = "T copy_ s1 | a1:R:A0+%d:%d" % (state, nbytes)
+    text = lambda: record(_launch("chap_grad_norm", _grad_norm(0x1000, 0x4000, state), "s0"), copy)
+    found = races(text())
+    assert len(found) == 1 and found[0]["fields"] == [("state:RW", "a1:R")] and "chap_grad_norm on s0" in found[0]["text"]
+    assert analyze(record(text().splitlines()[0], "ER e0 s0", "WE s1 e0", copy)) == []           # the reader's wait for its `ready` event
+    assert len(races(record(text().splitlines()[0], copy.replace("A0+%d:" % state, "A0+%d:" % (state + nbytes))))) == 0      # behind the last row
+    assert len(races(record(text().splitlines()[0], copy.replace(":%d" % nbytes, ":4").replace("+%d" % state, "+%d" % (state + nbytes - 4))))) == 1
+    monkeypatch.setitem(launch_access.MODES["chap_grad_norm"], "state", "R")
+    assert "state:R:" in text() and analyze(text()) == []
+
+
+# ---------------------------------------------------------------------------------------------------------------- the committed records
+def _golden(golden_dir, name):
+    return launch_order.read_record(os.path.join(golden_dir, name))
+
+
+@pytest.fixture(scope="module")
+def all_captured(golden_dir):
+    """The captured 2D step with teacher, guard and monitor attached (issue_trace.OPT_CASES['2d_all_captured'])."""
+    return _golden(golden_dir, "launch_order_2d_all_captured.txt.gz")
+
+
+@pytest.fixture(scope="module")
+def interval(golden_dir):
+    """issue_trace.record_interval(): three replays of that capture with a validation interval between the second and the third."""
+    return _golden(golden_dir, "launch_order_2d_all_interval.txt.gz")
+
+
+OPT_IN = ("chap_grad_norm", "chap_sgd_guard_step", "chap_monitor_accumulate", "chap_monitor_accumulate_labels", "chap_monitor_finalize")
+# Entry points of the record that no join protects, each with the reason: named here so that none is dropped silently.
+ALL_ON_ITS_OWN_STREAM = {
+    "chap_monitor_accumulate": "issued behind chap_pseudo_block on the capture's origin stream: both heads' pass-A logits are complete there (the forked "
+                               "decoder has been joined), the labels are the static batch, and its region of the workspace is read by the finalize "
+                               "launch on the same stream -- program order settles every conflict it has",
+}
+
+
+def _names(finding):
+    """the two launches of a finding, as (kind, name) pairs"""
+    return [tuple(w.split(": ")[1].split()[:2]) for w in (finding["a"], finding["b"])]
+
+
+def test_committed_opt_in_records_are_clean(all_captured, interval):
+    an = launch_order.Analysis(all_captured)
+    assert an.findings() == []
+    c = an.counts()
+    print(c)
+    assert c["launches"] > 500 and c["streams"] >= 4 and c["ordered_conflicts"] > 1000
+    names = [e.name for e in an.events if e.kind == "L"]
+    assert [names.count(n) for n in OPT_IN] == [1] * 5 and "chap_sgd_step" not in names and "chap_sgd_ema_step" not in names
+    opt = next(e for e in an.events if e.name == "chap_sgd_guard_step")
+    assert {f for f, m, _, _ in opt.acc} >= {"se.ema", "se.coef", "state"}                       # the teacher's average rides in the guarded launch
+    an = launch_order.Analysis(interval)
+    assert an.findings() == []
+    c = an.counts()
+    print(c)
+    assert c["replays"] == 3 and c["launches"] > 50 and c["torch_ops"] > 20 and c["streams"] >= 4
+
+
+def test_each_opt_in_launch_hangs_on_a_join_of_the_captured_step(all_captured):
+    """launch_order.join_table on the record with all three features: for the norm launch (it reads the buckets that the weight-gradient launches
+    of pass B's stream fill), the label-map accumulate (pass B's stream) and the finalize launch (the origin stream) at least one join is
+    necessary and the record without it has a finding that names the entry point.  profiles/launch_order_joins_opt.txt is this table."""
+    an = launch_order.Analysis(all_captured)
+    lines = an.lines
+    joins = launch_order.join_table(all_captured)
+    named = {n: [] for n in OPT_IN}
+    for n, ln, kind, extra in joins:
+        unit = (n - 1, n, n + 1) if ln.startswith("WS ") and lines[n].startswith("ER ") and lines[n + 1].startswith("WE ") else (n - 1,)
+        found = an.findings(skip=unit)
+        assert (len(found) > 0) == (kind == "necessary") and len(found) == extra
+        for name in OPT_IN:
+            k = sum(("L", name) in _names(f) for f in found)
+            if k:
+                named[name].append((n, ln, k))
+    for name, hits in named.items():
+        print("%-32s %s" % (name, hits))
+    for name in ("chap_grad_norm", "chap_monitor_accumulate_labels", "chap_monitor_finalize", "chap_sgd_guard_step"):
+        assert named[name], "no join of the record protects %s" % name
+    # ... and every other opt-in launch is listed with its reason, and the record bears the reason out
+    assert {n for n, hits in named.items() if not hits} == set(ALL_ON_ITS_OWN_STREAM)
+    for name in ALL_ON_ITS_OWN_STREAM:
+        mine = [i for i, e in enumerate(an.events) if e.name == name]
+        assert len(mine) == 1 and not any(mine[0] in key for key in an.pairs)                     # no conflict across streams at all
+        assert an.events[mine[0]].stream == lines[0].split()[2]                                   # the origin stream (line 1: the seed increment)
+    # the join behind pass B -- main.wait_stream(side) in ChapStep._iteration -- is one that all three hang on
+    origin = lines[0].split()[2]
+    side = next(e.stream for e in an.events if e.name == "chap_monitor_accumulate_labels")
+    assert side != origin
+    for name in ("chap_grad_norm", "chap_monitor_accumulate_labels", "chap_monitor_finalize"):
+        assert "WS %s %s" % (origin, side) in [ln for _, ln, _ in named[name]], name
+
+
+def _readers(text):
+    """[(line of the reader's wait for its `ready` event, line of its copy, line of the host's wait for its `copied` event)] of the device-to-host
+    copies between the second and the third replay that run on a stream of their own: StepMonitor.read(), then StepGuard.read()."""
+    lines = text.splitlines()
+    gr = [n for n, ln in enumerate(lines) if ln.startswith("GR ")]
+    main = lines[gr[0]].split()[1]
+    out = []
+    for n in range(gr[1], gr[2]):
+        f = lines[n].split(" | ")[0].split()
+        if f[:2] == ["T", "copy_"] and f[2] != main and ":W:" not in lines[n]:
+            assert lines[n - 2].split()[0] == "ER" and lines[n - 2].split()[2] == main             # ready.record(current stream)
+            assert lines[n - 1] == "WE %s %s" % (f[2], lines[n - 2].split()[1])
+            assert lines[n + 1] == "ER %s %s" % (lines[n + 1].split()[1], f[2]) and lines[n + 2] == "ES %s" % lines[n + 1].split()[1]
+            out.append((n - 1, n, n + 2))
+    return lines, gr, out
+
+
+def test_the_interval_record_has_both_readers_on_streams_of_their_own(interval):
+    lines, gr, readers = _readers(interval)
+    assert len(gr) == 3 and len(readers) == 2
+    (_, mon, _), (_, guard, _) = readers
+    assert lines[mon].split()[2] != lines[guard].split()[2]
+    size = lambda n: launch_order.parse_extent(lines[n].partition(" | ")[2].split(":", 2)[2])[1][2]
+    # the monitor's ring of 8 rows of 1 + 2 * (8 + 5 * 4) + 2 * 16 + 16 = 105 words; the guard's header and its 256 rows
+    assert size(mon) == 8 * 105 * 8 and size(guard) == 32 + 256 * 16
+
+
+@pytest.mark.parametrize("reader", ["monitor", "guard"])
+def test_a_reader_without_its_waits_meets_the_replays(interval, reader):
+    """The reader's `WE <own stream> <ready event>` taken out: its copy is no longer behind the replay that wrote what it copies.  The host's
+    wait for the copy (ES) taken out: the next replay may overwrite what is still being copied.
+
+    Each reader is checked in a record that holds it alone.  In the full record the guard's stream wait is IMPLIED: monitor.read() runs
+    first and ends with the host waiting for a copy that itself waited for the replay, so everything the host issues afterwards -- the guard's
+    copy included -- is behind that replay whatever the guard's own stream waits for (asserted below).  StepGuard.read() must not lean on
+    a monitor being attached, so the monitor's five lines are taken out before the guard's wait is."""
+    lines, gr, readers = _readers(interval)
+    mon, guard = readers
+    if reader == "guard":
+        an = launch_order.Analysis(interval)
+        assert an.findings(skip=guard[0]) == [], "the guard's stream wait used to be implied by the monitor reader's host wait"
+        assert (gr[1] + 1, guard[1] + 1) in [f["lines"] for f in an.findings(skip=(guard[0], mon[2]))]       # ... and by nothing else
+    other = guard if reader == "monitor" else mon
+    keep = [ln for n, ln in enumerate(lines) if not other[0] - 1 <= n <= other[2]]                # ER ready, WE, copy_, ER copied, ES
+    assert len(keep) == len(lines) - 5
+    text = "\n".join(keep) + "\n"
+    lines, gr, readers = _readers(text)
+    assert len(readers) == 1
+    wait, copy, host_wait = readers[0]
+    an = launch_order.Analysis(text)
+    assert an.findings() == []
+    found = an.findings(skip=wait)
+    print("%s reader without %r: %s" % (reader, lines[wait], [f["lines"] for f in found]))
+    assert (gr[1] + 1, copy + 1) in [f["lines"] for f in found]                                   # the replay just before the interval
+    assert all(copy + 1 in f["lines"] and _names(f)[0] == ("GR", "graph_replay") for f in found)
+    found = an.findings(skip=host_wait)
+    print("%s reader without %r: %s" % (reader, lines[host_wait], [f["lines"] for f in found]))
+    assert [f["lines"] for f in found] == [(copy + 1, gr[2] + 1)]                                 # the replay behind the interval
+    assert len(an.findings(skip=(wait, host_wait))) == 3                                          # all three replays write what the copy reads
+
+
 @pytest.fixture(scope="module")
 def captured_2d(golden_dir):
     with gzip.open(os.path.join(golden_dir, "launch_order_2d_captured.txt.gz"), "rt") as f:

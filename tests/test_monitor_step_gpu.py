@@ -5,7 +5,7 @@ subclass of the same step, and its loss words are out['mix_losses'] / out['vat_l
 eager; (d) a ring of four, eleven replays, no read: the last four rows and dropped == 7; (e) AblationStep scores its full-batch forward with
 n_first = labeled_bs; (f) train() of both entries with monitor=True writes monitor.csv and the reference's loss line and saves the same
 latest.pth as without; (g) one recorded monitored iteration has no unordered conflict (tests/launch_order.py), the three entry points
-described to the recorder by rules registered here."""
+described to the recorder by the access table (tests/launch_access.py)."""
 import functools
 import os
 
@@ -226,45 +226,15 @@ def test_f_train_3d_writes_the_monitor_files_and_the_same_weights(tmp_path):
                             seed=3), tmp_path)
 
 
-# ---- (g) the three entry points, described to the launch recorder: modes and extents of their pointers (tests/launch_access.py's tables
-# are plain dicts keyed by entry name; nothing of that file changes)
-R_, W_ = launch_access.R, launch_access.W
-
-
-def _region_a(p):
-    return launch_access.span(p.ws, ops.monitor_label_region(p.C) * 8)
-
-
-def _acc_rule(p):
-    px = p.N * p.P
-    return {"logits[0]": launch_access.span(p.logits[0], px * p.C * 4), "logits[1]": launch_access.span(p.logits[1], px * p.C * 4),
-            "labels": launch_access.span(p.labels, px * 8), "ws": _region_a(p)}
-
-
-def _lab_rule(p):
-    px, lr = p.N * p.P, ops.monitor_label_region(p.C)
-    return {"maps[0]": launch_access.span(p.maps[0], px * 8), "maps[1]": launch_access.span(p.maps[1], px * 8), "labels": launch_access.span(p.labels, px * 8),
-            "ws": launch_access.span(p.ws + lr * 8, (ops.monitor_ws_words(p.C) - lr) * 8)}
-
-
-def _fin_rule(p):
-    out = {"ws": launch_access.span(p.ws, ops.monitor_ws_words(p.C) * 8), "ring": launch_access.span(p.ring, p.ring_rows * ops.monitor_row_words(p.C) * 8),
-           "slot_iter": launch_access.span(p.slot_iter, 8)}
-    out.update({"scalars[%d]" % k: launch_access.span(p.scalars[k], 4) for k in range(p.nscalars)})
-    return out
-
-
-MONITOR_MODES = {"chap_monitor_accumulate": dict(logits=R_, labels=R_, ws=W_), "chap_monitor_accumulate_labels": dict(maps=R_, labels=R_, ws=W_),
-                 "chap_monitor_finalize": dict(ws=R_, ring=W_, slot_iter=R_, scalars=R_)}
-MONITOR_RULES = {"chap_monitor_accumulate": _acc_rule, "chap_monitor_accumulate_labels": _lab_rule, "chap_monitor_finalize": _fin_rule}
+# ---- (g) the three entry points are described to the launch recorder by tests/launch_access.py (MODES and RULES, hand-worked in
+# tests/test_launch_access_cpu.py): each accumulate launch writes its own region of the workspace, the finalize launch reads both
+MONITOR_ENTRIES = ("chap_monitor_accumulate", "chap_monitor_accumulate_labels", "chap_monitor_finalize")
 
 
 @pytest.mark.parametrize("mode", ["eager", "captured"])
-def test_g_a_monitored_iteration_has_no_unordered_conflict(mode, monkeypatch):
+def test_g_a_monitored_iteration_has_no_unordered_conflict(mode):
     from tests import issue_trace
-    for table, add in ((launch_access.MODES, MONITOR_MODES), (launch_access.RULES, MONITOR_RULES)):
-        for k, v in add.items():
-            monkeypatch.setitem(table, k, v)
+    assert all(name in launch_access.MODES and name in launch_access.RULES for name in MONITOR_ENTRIES)
     step, mon, (vd, ld, box, injd) = build(2, True)
     step.iter_num = 4500
     rec = issue_trace.RichRecorder(mode == "captured", issue_trace._Allocations(False), pack_entries=issue_trace._pack_entries_of(step.model))
@@ -276,7 +246,7 @@ def test_g_a_monitored_iteration_has_no_unordered_conflict(mode, monkeypatch):
     torch.cuda.synchronize()
     rich = rec.rich_text()
     launches = [ln for ln in rich.splitlines() if ln.startswith("L ")]
-    for name in MONITOR_MODES:
+    for name in MONITOR_ENTRIES:
         mine = [ln for ln in launches if ln.split()[1] == name]
         assert len(mine) == 1 and mine[0].partition(" | ")[2].strip(), name
     an = launch_order.Analysis(rich)
@@ -284,6 +254,6 @@ def test_g_a_monitored_iteration_has_no_unordered_conflict(mode, monkeypatch):
     assert an.counts()["ordered_conflicts"] > 0
     assert found == [], "%d unordered conflicts, the first:\n%s" % (len(found), "\n".join(f["text"] for f in found[:10]))
     # ... and the two accumulate launches sit on different streams, the finalize launch on the first one's
-    streams = {name: next(ln for ln in launches if ln.split()[1] == name).split(" | ")[0].split()[2] for name in MONITOR_MODES}
+    streams = {name: next(ln for ln in launches if ln.split()[1] == name).split(" | ")[0].split()[2] for name in MONITOR_ENTRIES}
     assert streams["chap_monitor_accumulate"] != streams["chap_monitor_accumulate_labels"]
     assert streams["chap_monitor_finalize"] == streams["chap_monitor_accumulate"]
