@@ -177,8 +177,9 @@ def attach_step(ctx, step, a):
 
 
 def replica_state(step):
-    """What must be bitwise equal on all ranks after every update: flat parameters, momentum and, with a mean teacher, its average."""
-    t = [step.model.flat_buffers()[0], step.opt.mom]
+    """What must be bitwise equal on all ranks after every update: flat parameters, the optimizer's state (SGD: momentum; Adam: both moments
+    and the state block with its step counter) and, with a mean teacher, its average."""
+    t = [step.model.flat_buffers()[0]] + list(step.opt.state_tensors())
     if step.teacher is not None:
         t.append(step.opt.ema)
     return t

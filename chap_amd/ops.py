@@ -615,6 +615,55 @@ def sgd_guard_step(param, grad, mom, lr_dev, momentum, weight_decay, state, ema=
 
 
 # ------------------------------------------------------------------------------------------
+# Adam / AdamW (include/chap_hip_optim.h; chap_amd.train.FusedAdamW owns the moments and the state block)
+ADAM_STATE_WORDS = 4                    # chap_adam_state: step | step_size | bc2_sqrt | decay
+
+
+def _adam_state_check(who, state, guard_state, dev):
+    if state.dtype != torch.int32 or state.numel() < ADAM_STATE_WORDS or state.device != dev or not state.is_contiguous():
+        raise ValueError("%s: state must be a contiguous int32 tensor of %d words on %s, got %s [%d] on %s"
+                         % (who, ADAM_STATE_WORDS, dev, state.dtype, state.numel(), state.device))
+    if guard_state is not None and (guard_state.dtype != torch.int32 or guard_state.numel() < guard_state_words(0) or guard_state.device != dev
+                                    or not guard_state.is_contiguous()):
+        raise ValueError("%s: guard_state must hold %d contiguous int32 words on %s" % (who, guard_state_words(0), dev))
+
+
+def adam_tick(state, lr_dev, beta1, beta2, weight_decay, decoupled, guard_state=None):
+    """Once per optimizer step, before adam_step: t = state[0] + 1 and, in fp64 and rounded once each, step_size = lr / (1 - beta1^t),
+    bc2_sqrt = sqrt(1 - beta2^t), decay = 1 - lr * weight_decay (`decoupled`) or 1, into `state`: an int32 tensor of ADAM_STATE_WORDS words.
+    With a `guard_state` (as grad_norm left it) whose skip flag is set nothing is written: a skipped step does not count."""
+    if lr_dev.dtype != torch.float32 or lr_dev.numel() < 1 or lr_dev.device != state.device:
+        raise ValueError("adam_tick: lr_dev must be an fp32 word on %s, got %s [%d] on %s" % (state.device, lr_dev.dtype, lr_dev.numel(), lr_dev.device))
+    _adam_state_check("adam_tick", state, guard_state, state.device)
+    p = L.AdamTickParams()
+    p.state, p.lr, p.guard = state.data_ptr(), lr_dev.data_ptr(), _p(guard_state)
+    p.beta1, p.beta2, p.weight_decay, p.decoupled = beta1, beta2, weight_decay, int(bool(decoupled))
+    L.call("chap_adam_tick", p, _stream())
+
+
+def adam_step(param, grad, exp_avg, exp_avg_sq, state, beta1, beta2, eps, weight_decay, decoupled, ema=None, coef_dev=None, guard_state=None,
+              grad_scale=1.0, zero_grad=True, grad2=None):
+    """One Adam (`decoupled` false: L2 weight decay, torch.optim.Adam) or AdamW (true) update of the flat fp32 buffers with the step size and
+    bias correction adam_tick left in `state`; the gradient is (grad + grad2) * fl32(grad_scale * guard_state.scale).  With `ema`, the same pass
+    averages the new parameters into it (coef_dev: two device words a, b).  A set skip flag in `guard_state`: nothing but the zeroing of the
+    buckets."""
+    n, dev = param.numel(), param.device
+    for name, t in (("param", param), ("grad", grad), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq), ("grad2", grad2), ("ema", ema)):
+        if t is not None and (t.dtype != torch.float32 or t.numel() != n or t.device != dev or not t.is_contiguous()):
+            raise ValueError("adam_step: %s must be a contiguous fp32 tensor of %d elements on %s, got %s [%d] on %s"
+                             % (name, n, dev, t.dtype, t.numel(), t.device))
+    _adam_state_check("adam_step", state, guard_state, dev)
+    if coef_dev is not None and (coef_dev.dtype != torch.float32 or coef_dev.numel() < 2 or coef_dev.device != dev):
+        raise ValueError("adam_step: coef_dev must hold two fp32 words on %s" % (dev,))
+    q = L.AdamParams()
+    q.param, q.grad, q.grad2, q.exp_avg, q.exp_avg_sq = param.data_ptr(), grad.data_ptr(), _p(grad2), exp_avg.data_ptr(), exp_avg_sq.data_ptr()
+    q.state, q.guard, q.ema, q.coef = state.data_ptr(), _p(guard_state), _p(ema), _p(coef_dev)
+    q.beta1, q.beta2, q.eps, q.weight_decay = beta1, beta2, eps, weight_decay
+    q.decoupled, q.grad_scale, q.zero_grad, q.n = int(bool(decoupled)), grad_scale, int(bool(zero_grad)), n
+    L.call("chap_adam_step", q, _stream())
+
+
+# ------------------------------------------------------------------------------------------
 # training monitor (include/chap_hip_monitor.h; chap_amd.monitor.StepMonitor owns the workspace and the ring)
 def monitor_group_words(C):
     return 8 + 5 * C                    # CHAP_MONITOR_GROUP_WORDS

@@ -66,21 +66,17 @@ def build_teacher(factory):
     return teacher
 
 
-class FusedSGD:
-    """optim.SGD(lr, momentum=0.9, weight_decay=1e-4) (train_ours_2D.py:278) as ONE kernel over the
-    model's flat parameter buffer; lr lives in device memory (graph replays pick up new values).
+class FusedOptimizer:
+    """What the optimizers of the captured step share: the flat parameter buffer of `model`, the learning rate as a word in device memory
+    (graph replays pick up new values; ChapStep moves it into its schedule block), the mean teacher's average and the gradient guard.
+    A subclass allocates its state and issues its kernels in step(); state_tensors() lists that state (what data-parallel replicas compare)
+    and state_dict() / load_state_dict() carry it through a checkpoint, tagged with `kind`."""
 
-    `ema` (a flat fp32 tensor of the parameter buffer's size: the mean teacher's parameters): the same launch also averages the weights
-    into it, ema = a * ema + b * param (update_ema_variables, :50-54), with (a, b) = `ema_coef`, two fp32 words in device memory that
-    set_ema_step() -- or the owner of the words, ChapStep's schedule block -- fills before every step.
+    kind = None
 
-    `guard` (chap_amd.guard.StepGuard): step() first takes the norm of the gradient it is about to apply (chap_grad_norm) and then issues the
-    guarded form of the same kernel, which reads the clip coefficient and the skip flag from the guard's state block."""
-
-    def __init__(self, model, lr, momentum=0.9, weight_decay=1e-4, ema=None, ema_decay=0.99, guard=None):
-        self.model, self.momentum, self.weight_decay = model, momentum, weight_decay
-        flat, grad = model.flat_buffers()
-        self.mom = torch.zeros_like(flat)
+    def __init__(self, model, lr, ema=None, ema_decay=0.99, guard=None):
+        self.model = model
+        flat = model.flat_buffers()[0]
         self.lr_dev = torch.full((1,), float(lr), dtype=torch.float32, device=flat.device)
         self.param_groups = [{"lr": float(lr)}]
         self.ema, self.ema_decay, self.ema_coef, self.ema_model = None, float(ema_decay), None, None
@@ -94,15 +90,15 @@ class FusedSGD:
         """None detaches it: step() is the unguarded launch again."""
         flat = self.model.flat_buffers()[0]
         if guard is not None and (guard.ws is None or guard.ws.device != flat.device):
-            raise ValueError("chap_amd FusedSGD: the guard lives on %s, the parameters on %s" % (guard.device, flat.device))
+            raise ValueError("chap_amd %s: the guard lives on %s, the parameters on %s" % (type(self).__name__, guard.device, flat.device))
         self.guard = guard
 
     def set_ema(self, ema, model=None):
         """`model`: the module whose parameters are views of `ema` (its packed weight copies go stale with every step)."""
         flat = self.model.flat_buffers()[0]
         if ema.dtype != torch.float32 or ema.shape != flat.shape or ema.device != flat.device or not ema.is_contiguous():
-            raise ValueError("chap_amd FusedSGD: ema must be a contiguous fp32 tensor of the flat parameter buffer's shape %s on %s, got %s %s on %s"
-                             % (tuple(flat.shape), flat.device, ema.dtype, tuple(ema.shape), ema.device))
+            raise ValueError("chap_amd %s: ema must be a contiguous fp32 tensor of the flat parameter buffer's shape %s on %s, got %s %s on %s"
+                             % (type(self).__name__, tuple(flat.shape), flat.device, ema.dtype, tuple(ema.shape), ema.device))
         self.ema, self.ema_model = ema, model
         if self.ema_coef is None:
             self.ema_coef = torch.tensor([0.0, 1.0], dtype=torch.float32, device=flat.device)
@@ -118,6 +114,46 @@ class FusedSGD:
     def zero_grad(self, set_to_none=False):
         pass                                   # the step kernel zeroes the gradient buffer
 
+    def state_tensors(self):
+        raise NotImplementedError
+
+    def state_dict(self):
+        raise NotImplementedError
+
+    def _check_kind(self, st):
+        got = st.get("kind") if isinstance(st, dict) else None
+        if got != self.kind:
+            raise ValueError("chap_amd %s: the optimizer state is of kind %r, this optimizer's is %r" % (type(self).__name__, got, self.kind))
+
+
+class FusedSGD(FusedOptimizer):
+    """optim.SGD(lr, momentum=0.9, weight_decay=1e-4) (train_ours_2D.py:278) as ONE kernel over the
+    model's flat parameter buffer; lr lives in device memory (graph replays pick up new values).
+
+    `ema` (a flat fp32 tensor of the parameter buffer's size: the mean teacher's parameters): the same launch also averages the weights
+    into it, ema = a * ema + b * param (update_ema_variables, :50-54), with (a, b) = `ema_coef`, two fp32 words in device memory that
+    set_ema_step() -- or the owner of the words, ChapStep's schedule block -- fills before every step.
+
+    `guard` (chap_amd.guard.StepGuard): step() first takes the norm of the gradient it is about to apply (chap_grad_norm) and then issues the
+    guarded form of the same kernel, which reads the clip coefficient and the skip flag from the guard's state block."""
+
+    kind = "sgd"
+
+    def __init__(self, model, lr, momentum=0.9, weight_decay=1e-4, ema=None, ema_decay=0.99, guard=None):
+        self.momentum, self.weight_decay = momentum, weight_decay
+        self.mom = torch.zeros_like(model.flat_buffers()[0])
+        super().__init__(model, lr, ema, ema_decay, guard)
+
+    def state_tensors(self):
+        return [self.mom]
+
+    def state_dict(self):
+        return {"kind": "sgd", "momentum": self.mom.detach().clone()}
+
+    def load_state_dict(self, st):
+        self._check_kind(st)
+        self.mom.copy_(st["momentum"])
+
     def step(self, grad_scale=1.0, grad2=None):
         flat, grad = self.model.flat_buffers()
         if self.guard is not None:              # behind the gradient exchange: the norm of what is applied, the same word on every rank
@@ -132,6 +168,83 @@ class FusedSGD:
             if self.ema_model is not None:
                 self.ema_model.mark_params_dirty()
         self.model.mark_params_dirty()
+
+
+class FusedAdamW(FusedOptimizer):
+    """torch.optim.AdamW(lr, betas, eps, weight_decay) -- `decoupled=False`: torch.optim.Adam with its L2 weight decay -- over the model's flat
+    parameter buffer, as two launches (include/chap_hip_optim.h): chap_adam_tick advances the step counter t and forms lr / (1 - beta1^t),
+    sqrt(1 - beta2^t) and 1 - lr * weight_decay in a 16-byte state block in device memory, chap_adam_step is the streaming update that reads
+    them.  The counter lives on the device: a replayed graph needs no host upload, and a step the guard skips does not count (torch's t when
+    step() is not called).  `ema` and `guard` as FusedSGD's: the average is part of the same launch, the clip coefficient and the skip flag are
+    read from the guard's state block.  No AMSGrad, one group of hyper-parameters for all parameters."""
+
+    kind = "adam"
+
+    def __init__(self, model, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, decoupled=True, ema=None, ema_decay=0.99, guard=None):
+        b1, b2 = float(betas[0]), float(betas[1])
+        if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+            raise ValueError("chap_amd FusedAdamW: betas=%r, need 0 <= beta < 1" % (tuple(betas),))
+        if not eps > 0.0:
+            raise ValueError("chap_amd FusedAdamW: eps=%r, need eps > 0" % (eps,))
+        self.betas, self.eps, self.weight_decay, self.decoupled = (b1, b2), float(eps), float(weight_decay), bool(decoupled)
+        flat = model.flat_buffers()[0]
+        self.exp_avg, self.exp_avg_sq = torch.zeros_like(flat), torch.zeros_like(flat)
+        self.state = torch.zeros(ops.ADAM_STATE_WORDS, dtype=torch.int32, device=flat.device)       # chap_adam_state
+        super().__init__(model, lr, ema, ema_decay, guard)
+
+    def state_tensors(self):
+        return [self.exp_avg, self.exp_avg_sq, self.state]
+
+    def state_dict(self):
+        return {"kind": "adam", "exp_avg": self.exp_avg.detach().clone(), "exp_avg_sq": self.exp_avg_sq.detach().clone(),
+                "state": self.state.detach().clone()}
+
+    def load_state_dict(self, st):
+        self._check_kind(st)
+        self.exp_avg.copy_(st["exp_avg"])
+        self.exp_avg_sq.copy_(st["exp_avg_sq"])
+        self.state.copy_(st["state"])
+
+    def step(self, grad_scale=1.0, grad2=None):
+        flat, grad = self.model.flat_buffers()
+        gs = None
+        if self.guard is not None:              # behind the gradient exchange, as FusedSGD.step
+            self.guard.launch_norm(grad, grad2, grad_scale)
+            gs = self.guard.state
+        ops.adam_tick(self.state, self.lr_dev, self.betas[0], self.betas[1], self.weight_decay, self.decoupled, gs)
+        ops.adam_step(flat, grad, self.exp_avg, self.exp_avg_sq, self.state, self.betas[0], self.betas[1], self.eps, self.weight_decay, self.decoupled,
+                      self.ema, self.ema_coef if self.ema is not None else None, gs, grad_scale, True, grad2)
+        if self.ema_model is not None:
+            self.ema_model.mark_params_dirty()
+        self.model.mark_params_dirty()
+
+
+OPTIMIZERS = ("sgd", "adam", "adamw")
+
+
+def check_optimizer(name, who="chap_amd"):
+    """The optimizers the train() entries build.  They call this before anything is allocated or written."""
+    if name not in OPTIMIZERS:
+        raise ValueError("%s: optimizer=%r; choose one of %s" % (who, name, ", ".join(OPTIMIZERS)))
+
+
+def optimizer_line(args):
+    """The line of log.txt that names an Adam run's optimizer and its hyper-parameters (a default run's log is what it always was: no line)."""
+    name = args["optimizer"]
+    b = args.get("betas", (0.9, 0.999))
+    return "optimizer %s: base_lr %g, betas (%g, %g), eps %g, weight_decay %g (%s)" % (
+        name, args["base_lr"], b[0], b[1], args.get("adam_eps", 1e-8), args.get("weight_decay", 1e-4), "decoupled" if name == "adamw" else "L2")
+
+
+def build_optimizer(model, args):
+    """args['optimizer']: 'sgd' (default) -> FusedSGD(base_lr, momentum, weight_decay); 'adam' / 'adamw' -> FusedAdamW(base_lr, betas, adam_eps,
+    weight_decay) with L2 / decoupled weight decay."""
+    name = args.get("optimizer", "sgd")
+    check_optimizer(name)
+    if name == "sgd":
+        return FusedSGD(model, args["base_lr"], args["momentum"], args["weight_decay"])
+    return FusedAdamW(model, args["base_lr"], tuple(args.get("betas", (0.9, 0.999))), args.get("adam_eps", 1e-8), args["weight_decay"],
+                      decoupled=(name == "adamw"))
 
 
 def _distinct_streams(dev, n):
@@ -312,7 +425,7 @@ class ChapStep:
         a = dict(DEFAULT_ARGS)
         a.update(args or {})
         self.args, self.model = a, model
-        self.opt = optimizer or FusedSGD(model, a["base_lr"], a["momentum"], a["weight_decay"])
+        self.opt = optimizer or build_optimizer(model, a)
         self.adv_loss = VAT2d(xi=a["noise_mag"], epi=a["epi"], num_classes=a["num_classes"], ip=a["vat_iters"], sign=a["vat_sign"])
         dev = self.opt.lr_dev.device
         self.dims = getattr(model, "dims", 2)
@@ -334,14 +447,14 @@ class ChapStep:
         self._sched_ev, self._sched_k = [None] * 4, 0
         self.box = self._sched[:nbox]
         self.cw_dev = self._sched[6:7].view(torch.float32)
-        if isinstance(self.opt, FusedSGD):                       # the optimizer reads its lr from the same block
+        if isinstance(self.opt, FusedOptimizer):                 # the optimizer reads its lr from the same block
             self._sched[7:8].view(torch.float32).copy_(self.opt.lr_dev)
             self.opt.lr_dev = self._sched[7:8].view(torch.float32)
         if teacher is not None:
             self._attach_teacher(teacher)
         self.guard = guard
         if guard is not None:
-            if not isinstance(self.opt, FusedSGD):
+            if not isinstance(self.opt, FusedOptimizer):
                 raise ValueError("chap_amd ChapStep: a gradient guard needs the fused optimizer (FusedSGD): clip and skip are part of that kernel")
             self.opt.set_guard(guard)
         self.iter_num = 0
@@ -394,7 +507,7 @@ class ChapStep:
         flat parameter buffer is what the optimizer kernel averages the student's weights into, with the coefficients in words 8-9 of the
         schedule block.  It is never run by the iteration: evaluate it after sync_teacher_stats()."""
         model = self.model
-        if not isinstance(self.opt, FusedSGD):
+        if not isinstance(self.opt, FusedOptimizer):
             raise ValueError("chap_amd ChapStep: a mean teacher needs the fused optimizer (FusedSGD): its average is part of that kernel")
         if teacher is model or type(teacher) is not type(model):
             raise ValueError("chap_amd ChapStep: the teacher must be a second instance of %s, got %s" % (type(model).__name__, type(teacher).__name__))
@@ -465,7 +578,7 @@ class ChapStep:
         if self.monitor is not None:
             self.monitor.advance()
         lr_ = a["base_lr"] * (1.0 - self.iter_num / a["max_iterations"]) ** 0.9
-        if isinstance(self.opt, FusedSGD):
+        if isinstance(self.opt, FusedOptimizer):
             self.opt.param_groups[0]["lr"] = float(lr_)          # reaches the device with the next step's schedule block
         else:
             self.opt.set_lr(lr_)
@@ -475,14 +588,18 @@ class ChapStep:
     def state_dict(self):
         """Everything a long run needs to continue exactly where it stopped.  'model' is the reference's checkpoint
         (what train_ours_2D.py:428-435 saves with torch.save(model.state_dict())); the rest is absent upstream:
-        momentum buffer, iteration counter (drives poly LR and the consistency ramp), numpy RNG state (BCP box
+        momentum buffer ('momentum'; with Adam 'optimizer' instead: its moments and state block), iteration counter (drives poly LR and the consistency ramp), numpy RNG state (BCP box
         offsets) and the dropout / VAT noise RNG epoch.  With a mean teacher: 'ema', its flat parameter buffer."""
         rng = self.model._rng
         st = {"model": {k: v.detach().clone() for k, v in self.model.state_dict().items()},
-                "momentum": self.opt.mom.detach().clone(), "iter_num": int(self.iter_num),
+                "iter_num": int(self.iter_num),
                 "lr": float(self.opt.param_groups[0]["lr"]), "numpy_rng": np.random.get_state(),
                 "rng": {"base": rng.base, "count": rng.count, "seed_dev": int(rng.seed_dev.item())},
                 "gradsim": None if self.gradsim is None else [sc.detach().clone() for sc in self.gradsim.get_sim()]}
+        if isinstance(self.opt, FusedOptimizer) and self.opt.kind != "sgd":     # Adam: both moments and the four words of its state block
+            st["optimizer"] = self.opt.state_dict()
+        else:                                   # SGD keeps the key it always had
+            st["momentum"] = self.opt.mom.detach().clone()
         if self.teacher is not None:
             st["ema"] = self.opt.ema.detach().clone()
         if self.guard is not None:
@@ -490,8 +607,16 @@ class ChapStep:
         return st
 
     def load_state_dict(self, st):
+        if isinstance(self.opt, FusedOptimizer):         # before anything is changed: the checkpoint carries this optimizer's kind of state
+            have = st["optimizer"].get("kind") if isinstance(st.get("optimizer"), dict) else ("sgd" if "momentum" in st else None)
+            if have != self.opt.kind:
+                raise ValueError("chap_amd ChapStep: the checkpoint carries optimizer state of kind %r, the step's optimizer (%s) needs %r"
+                                 % (have, type(self.opt).__name__, self.opt.kind))
         self.model.load_state_dict(st["model"], strict=True)
-        self.opt.mom.copy_(st["momentum"])
+        if isinstance(self.opt, FusedOptimizer):
+            self.opt.load_state_dict(st["optimizer"] if self.opt.kind != "sgd" else {"kind": "sgd", "momentum": st["momentum"]})
+        else:
+            self.opt.mom.copy_(st["momentum"])
         self.iter_num = int(st["iter_num"])
         self.opt.set_lr(st["lr"])
         np.random.set_state(st["numpy_rng"])

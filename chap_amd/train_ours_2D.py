@@ -34,13 +34,14 @@ from .guard import StepGuard, check_finite_before_save, flush_to_run as flush_gu
 from .monitor import StepMonitor
 from .networks.net_factory import net_factory
 from .synthetic import synthetic_batch
-from .train import DEFAULT_ARGS, ChapStep, build_teacher, check_num_classes
+from .train import DEFAULT_ARGS, ChapStep, build_teacher, check_num_classes, check_optimizer, optimizer_line
 
 FLAG_DEFAULTS = dict(DEFAULT_ARGS, model="dualdecoder", decoder_type="mcnet", gpu=0, seed=1337, image_size=[256, 256],
                      val_interval=200, labeled_num=7, use_graph=True,          # train_ours_2D.py:469-526
                      mean_teacher=False, ema_decay=0.99,                       # --ema_decay (:499); mean_teacher: the commented-out ema_model (:251)
                      monitor=False,                                            # chap_amd.monitor: monitor.csv and the loss line of :404-405
                      clip_grad_norm=0.0, skip_nonfinite=False,                 # chap_amd.guard: clip by the global gradient norm (0 = off), skip non-finite steps; guard.csv
+                     optimizer="sgd", betas=(0.9, 0.999), adam_eps=1e-8,               # chap_amd.train.FusedAdamW: 'adam' (L2 weight decay) / 'adamw' (decoupled) with base_lr, weight_decay
                      data_parallel=False, dp_backend="nccl", dp_timeout_s=600, dp_force_group=False, dp_noise_per_rank=True)      # chap_amd.distributed
 
 
@@ -57,6 +58,7 @@ def train(args, snapshot_path):
     a = dict(FLAG_DEFAULTS)
     a.update(args)
     check_num_classes(a["num_classes"], "chap_amd.train_ours_2D")
+    check_optimizer(a["optimizer"], "chap_amd.train_ours_2D")
     ctx = init_rank(a)                          # the plain single process unless args["data_parallel"]
     log = logging.getLogger("chap_amd.train")
     log.setLevel(logging.INFO)
@@ -66,6 +68,8 @@ def train(args, snapshot_path):
             os.makedirs(snapshot_path, exist_ok=True)
             fh = logging.FileHandler(os.path.join(snapshot_path, "log.txt"))
             log.addHandler(fh)
+        if a["optimizer"] != "sgd":              # (the default run's log is what it always was)
+            log.info(optimizer_line(a))
         model = _run(a, snapshot_path, ctx, log)
         ctx.barrier()
     finally:                    # also when the loop raises: leave the process groups, and a later train() in this process must not log into this file

@@ -32,12 +32,13 @@ from .networks.vnet import DualDecoder3d, VNet
 from .synthetic import synthetic_batch_3d
 from . import metrics
 from . import test_3d_patch as T3P
-from .train import DEFAULT_ARGS, ChapStep, build_teacher, check_num_classes
+from .train import DEFAULT_ARGS, ChapStep, build_teacher, check_num_classes, check_optimizer, optimizer_line
 
 FLAG_DEFAULTS = dict(DEFAULT_ARGS, model="dualdecoder", num_classes=2, patch_size=[112, 112, 80], batch_size=4, labeled_bs=2,
                      stride_xy=18, stride_z=4, val_interval=200, use_graph=True, gpu=0, seed=1337,
                      mean_teacher=False, ema_decay=0.99, monitor=False,       # as train_ours_2D: --ema_decay (train_ours_2D.py:499), the ema_model of :251
                      clip_grad_norm=0.0, skip_nonfinite=False,                # chap_amd.guard, as train_ours_2D
+                     optimizer="sgd", betas=(0.9, 0.999), adam_eps=1e-8,               # chap_amd.train.FusedAdamW: 'adam' (L2 weight decay) / 'adamw' (decoupled) with base_lr, weight_decay
                      data_parallel=False, dp_backend="nccl", dp_timeout_s=600, dp_force_group=False, dp_noise_per_rank=True)      # chap_amd.distributed
 
 
@@ -67,6 +68,7 @@ def train(args, snapshot_path):
     a = dict(FLAG_DEFAULTS)
     a.update(args)
     check_num_classes(a["num_classes"], "chap_amd.train_ours_3D")
+    check_optimizer(a["optimizer"], "chap_amd.train_ours_3D")
     ctx = init_rank(a)                          # the plain single process unless args["data_parallel"]
     log = logging.getLogger("chap_amd.train3d")
     log.setLevel(logging.INFO)
@@ -76,6 +78,8 @@ def train(args, snapshot_path):
             os.makedirs(snapshot_path, exist_ok=True)
             fh = logging.FileHandler(os.path.join(snapshot_path, "log.txt"))
             log.addHandler(fh)
+        if a["optimizer"] != "sgd":              # (the default run's log is what it always was)
+            log.info(optimizer_line(a))
         device = ctx.device
         if ctx.group is not None:
             torch.cuda.set_device(device)
