@@ -379,6 +379,27 @@ __device__ __forceinline__ void tile_coords(long tile, int tiles_x, int tiles_y,
 template <int KC, bool D3, typename T = bf16_t> constexpr int conv_min_waves() { return CHAP_CONV_MINWAVES > 1 ? CHAP_CONV_MINWAVES : (KC == 16 && !D3 ? 3 : (sizeof(T) == 2 ? 2 : 1)); }
 template <typename T> constexpr bool conv_one_wbuf() { return sizeof(T) == 2; }      // staged weights: ONE LDS buffer (bf16) / two (fp32)
 
+// The epilogue's per-lane output offsets depend on (t, m) only, so the compiler hoists every one of them out of the item loop -- as 64-bit values,
+// once per store flavour (fp32 / bf16 vector stores, element stores per channel): 36 register pairs in the NT 4 x MR 2 instances, all of them live
+// across the MFMA loop and all of them spilled under the 256-register bound (profiles/spill_audit_resource_usage.txt).  conv_pin() redefines the
+// 32-bit value they derive from at its point of use as far as the compiler can tell (no instruction), so the sums stay in the epilogue: a shift
+// and an add per store.  bf16 only (conv_pin_offsets).
+// Bias and statistics shift of the block's 16 NT output channels in LDS instead of 8 NT registers held across the item loop (conv_wp_kernel does the
+// same): the instances that still spill with them in registers -- 2D k2 s2 with 64 output channels per block and staged or streamed weights.  No new
+// LDS bytes: until the statistics flush at the end of the kernel wave 3's two rows of bstat are free, [bias | shift][16 NT].
+template <typename T, int KS, int ST, bool D3, int NT, bool WLDS> constexpr bool conv_bias_lds() { return sizeof(T) == 2 && KS == 2 && ST == 2 && !D3 && NT == 4 && !WLDS; }
+
+template <bool PIN, typename V> __device__ __forceinline__ V conv_pin(V v) {
+    if constexpr (PIN) asm volatile("" : "+v"(v));
+    return v;
+}
+// 3D geometries size their persistent grid by the blocks that FIT a CU (conv_dispatch.inc), so an instance that the pin takes over an occupancy step
+// would get another grid and deal its BatchNorm statistics to other slots: there only the instances that sit on the 256-register bound with spills
+// are pinned (bricks from 32 output channels, 32-channel chunks or the add; everything with 64 output channels).  2D grids are capped at two blocks per CU.
+template <typename T, bool D3, int KC, int NT, bool ADD2, bool ZW> constexpr bool conv_pin_offsets() {
+    return sizeof(T) == 2 && (!D3 || (ZW ? (NT >= 2 || KC == 32 || ADD2) : NT == 4));
+}
+
 template <typename T, int KS, int ST, bool D3, int KC, int NT, int MR, bool ADD2, bool WLDS, bool ZW = false, bool ONE = false>
 __device__ __forceinline__ void conv_fwd_kernel(const chap_conv_params& P) {
     typedef conv_geom<KS, ST, D3, MR, ZW> G;
@@ -489,12 +510,17 @@ __device__ __forceinline__ void conv_fwd_kernel(const chap_conv_params& P) {
     constexpr bool WST = !WLDS && conv_wstaged<T, KS, ST, D3, KC, NT, MR, ZW>();
     constexpr int WFR = WST ? (STEPS * NT + 3) / 4 : 1;          // fragments per thread (wave w takes blocks w, w+4, ..)
     F wreg[WFR];
+    // (the wave index as a scalar.  From threadIdx it is a per-lane value as far as the compiler can tell, and the block offsets of the WFR fragments --
+    //  wave-uniform in fact -- become 64-bit lane offsets that it keeps across the item loop.  Only where those registers were spilled: elsewhere the
+    //  scalar form costs scalar registers the instance does not have, and in 3D a step of occupancy would move the persistent grid, see conv_pin_offsets)
+    constexpr bool WVS = conv_bias_lds<T, KS, ST, D3, NT, WLDS>() || (D3 && conv_pin_offsets<T, D3, KC, NT, ADD2, ZW>());
+    const int wv = WVS ? __builtin_amdgcn_readfirstlane(wave) : wave;
     auto wstage_issue = [&](int chunk_) {
         if constexpr (WST) {
             const T* src = (const T*)P.wpacked + (long)chunk_ * STEPS * wstep + lane * 8;
 #pragma unroll
             for (int k = 0; k < WFR; ++k) {
-                const int i = min(4 * k + wave, STEPS * NT - 1);  // clamp (wave-uniform): no branch around the load
+                const int i = min(4 * k + wv, STEPS * NT - 1);    // clamp (wave-uniform): no branch around the load
                 const int step = i / NT, t = i % NT;
                 const int tt = nt0 + t < ntiles_total ? nt0 + t : nt0;          // clamp: those channels are never stored
                 wreg[k] = frag<T>::load(src + (long)step * wstep + (long)tt * 512);
@@ -506,7 +532,7 @@ __device__ __forceinline__ void conv_fwd_kernel(const chap_conv_params& P) {
             T* dst = wlds + (size_t)buf * (STEPS * NT * 512) + lane * 8;
 #pragma unroll
             for (int k = 0; k < WFR; ++k) {
-                const int i = min(4 * k + wave, STEPS * NT - 1);  // clamped waves rewrite the last block with identical data: every prefetch register is consumed on every path
+                const int i = min(4 * k + wv, STEPS * NT - 1);    // clamped waves rewrite the last block with identical data: every prefetch register is consumed on every path
                 frag<T>::store(dst + i * 512, wreg[k]);
             }
         }
@@ -531,6 +557,11 @@ __device__ __forceinline__ void conv_fwd_kernel(const chap_conv_params& P) {
 
     f32x4 acc[MR][NT];
     float ssum[NT][4], ssq[NT][4], bj[NT][4], cj[NT][4];        // cj: shift of the statistics (moments of v - c)
+    constexpr bool PINO = conv_pin_offsets<T, D3, KC, NT, ADD2, ZW>();
+    constexpr bool BCL = conv_bias_lds<T, KS, ST, D3, NT, WLDS>();      // bias / shift in LDS, bj / cj unused
+    static_assert(!BCL || 2 * 16 * NT <= 256, "one thread per bias / shift value");
+    float* bc = bstat + 3 * 2 * 16 * NT;
+    float bcv = 0.f; bool bcok = false;
     // bias: all loads first (index clamped, no branch, no use in between), the selects afterwards -- a use right
     // behind each load makes the compiler wait for it (and for every prefetch issued above) NT*4 times in a row
     {
@@ -544,9 +575,17 @@ __device__ __forceinline__ void conv_fwd_kernel(const chap_conv_params& P) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 ssum[t][j] = 0.f; ssq[t][j] = 0.f;
-                bj[t][j] = bsrc[(P.bias && nl + j < P.Cout) ? cb + j : 0];
-                cj[t][j] = csrc[(has_shift && nl + j < P.Cout) ? cb + j : 0];
+                if constexpr (!BCL) {
+                    bj[t][j] = bsrc[(P.bias && nl + j < P.Cout) ? cb + j : 0];
+                    cj[t][j] = csrc[(has_shift && nl + j < P.Cout) ? cb + j : 0];
+                }
             }
+        }
+        if constexpr (BCL) {                                     // thread i < 16 NT: bias of channel nt0 * 16 + i; the next 16 NT threads: the shift (clamped index, no branch)
+            const int which = threadIdx.x / (16 * NT), nl = nt0 * 16 + (int)threadIdx.x % (16 * NT);
+            const int cb = P.out_mode == 1 ? (nl % P.out_Cn) : nl;
+            bcok = (which == 0 ? P.bias != nullptr : (which == 1 && has_shift)) && nl < P.Cout;
+            bcv = *(const float*)((const char*)bsrc + (which == 1 ? (const char*)csrc - (const char*)bsrc : 0l) + (bcok ? cb : 0) * (long)sizeof(float));
         }
     }
     // ---- now the dependent LDS stores
@@ -562,6 +601,7 @@ __device__ __forceinline__ void conv_fwd_kernel(const chap_conv_params& P) {
             }
         }
     }
+    if (BCL && threadIdx.x < 2 * 16 * NT) bc[threadIdx.x] = bcok ? bcv : 0.f;
     if (WLDS) {
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
@@ -579,6 +619,7 @@ __device__ __forceinline__ void conv_fwd_kernel(const chap_conv_params& P) {
             }
         }
     }
+    if constexpr (!BCL) {
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
         const int nl = (nt0 + t) * 16 + 4 * g;
@@ -592,6 +633,7 @@ __device__ __forceinline__ void conv_fwd_kernel(const chap_conv_params& P) {
     for (int t = 0; t < NT; ++t)
 #pragma unroll
         for (int j = 0; j < 4; ++j) { asm volatile("" : "+v"(bj[t][j])); asm volatile("" : "+v"(cj[t][j])); }   // land the bias loads here, not behind the first prefetch of the item loop
+    }
     const bool do_stats = P.stats != nullptr;
     const int SD2 = (P.dims == 3) ? 2 : 1;
     // per-lane output offsets relative to the tile origin (elements), one per (t): row term added per m
@@ -710,18 +752,25 @@ __device__ __forceinline__ void conv_fwd_kernel(const chap_conv_params& P) {
                 const long plane = (long)P.D * P.H * P.W;
 #pragma unroll
                 for (int t = 0; t < NT; ++t) {
-                    const int nl = (nt0 + t) * 16 + 4 * g;        // logical output channel of j = 0
+                    const int nl = conv_pin<PINO>((nt0 + t) * 16 + 4 * g);        // logical output channel of j = 0
+                    const int oo = conv_pin<PINO>(ooff[t]);
+                    float bjt[4], cjt[4];
+                    if constexpr (BCL) { ld4(bc + t * 16 + 4 * g, bjt); ld4(bc + 16 * NT + t * 16 + 4 * g, cjt); }
+                    else {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) { bjt[j] = bj[t][j]; cjt[j] = cj[t][j]; }
+                    }
 #pragma unroll
                     for (int m = 0; m < MR; ++m) {
                         const int row = ZW ? m : wave * MR + m;
                         const bool valid = xok && zok && (y0 + row < P.H) && nl < P.Cout;
                         float v[4];
 #pragma unroll
-                        for (int j = 0; j < 4; ++j) v[j] = acc[m][t][j] + bj[t][j];
+                        for (int j = 0; j < 4; ++j) v[j] = acc[m][t][j] + bjt[j];
                         if (!valid) continue;
 #pragma unroll
-                        for (int j = 0; j < 4; ++j) { const float vs = v[j] - cj[t][j]; ssum[t][j] += vs; ssq[t][j] += vs * vs; }
-                        const long oi = o0 + row * orow + zw_off + ooff[t];
+                        for (int j = 0; j < 4; ++j) { const float vs = v[j] - cjt[j]; ssum[t][j] += vs; ssq[t][j] += vs * vs; }
+                        const long oi = o0 + row * orow + zw_off + oo;
 #pragma unroll
                         for (int j = 0; j < 4; ++j) if (nl + j < P.Cout) {
                             if (P.out_planar) ((float*)P.out)[oi + (nl + j) * plane] = v[j];
@@ -742,17 +791,24 @@ __device__ __forceinline__ void conv_fwd_kernel(const chap_conv_params& P) {
                     for (int t = 0; t < NT; ++t) {
                         const bool cok = (nt0 + t) * 16 + 4 * g < P.Cout;
                         char* obt = (P.out2 && (nt0 + t) * 16 >= P.out2_from) ? ob2 : ob;      // wave-uniform
+                        const int oo = conv_pin<PINO>(ooff[t]);
+                        float bjt[4], cjt[4];
+                        if constexpr (BCL) { ld4(bc + t * 16 + 4 * g, bjt); ld4(bc + 16 * NT + t * 16 + 4 * g, cjt); }
+                        else {
+#pragma unroll
+                            for (int j = 0; j < 4; ++j) { bjt[j] = bj[t][j]; cjt[j] = cj[t][j]; }
+                        }
 #pragma unroll
                         for (int m = 0; m < MR; ++m) {
                             const int row = ZW ? m : wave * MR + m;
                             const bool valid = decltype(FULL)::value || (xok && zok && cok && (y0 + row < P.H));
                             float v[4];
                             // packed fp32 (v_pk_add_f32 / v_pk_fma_f32): bias, shifted moments -- the epilogue is VALU time of a VALU-bound kernel
-                            const f32x2 v0 = (f32x2){acc[m][t][0], acc[m][t][1]} + (f32x2){bj[t][0], bj[t][1]};
-                            const f32x2 v1 = (f32x2){acc[m][t][2], acc[m][t][3]} + (f32x2){bj[t][2], bj[t][3]};
+                            const f32x2 v0 = (f32x2){acc[m][t][0], acc[m][t][1]} + (f32x2){bjt[0], bjt[1]};
+                            const f32x2 v1 = (f32x2){acc[m][t][2], acc[m][t][3]} + (f32x2){bjt[2], bjt[3]};
                             v[0] = v0.x; v[1] = v0.y; v[2] = v1.x; v[3] = v1.y;
                             if (do_stats) {
-                                f32x2 d0 = v0 - (f32x2){cj[t][0], cj[t][1]}, d1 = v1 - (f32x2){cj[t][2], cj[t][3]};
+                                f32x2 d0 = v0 - (f32x2){cjt[0], cjt[1]}, d1 = v1 - (f32x2){cjt[2], cjt[3]};
                                 if (!decltype(FULL)::value) { d0.x = valid ? d0.x : 0.f; d0.y = valid ? d0.y : 0.f; d1.x = valid ? d1.x : 0.f; d1.y = valid ? d1.y : 0.f; }
                                 const f32x2 s0 = (f32x2){ssum[t][0], ssum[t][1]} + d0, s1 = (f32x2){ssum[t][2], ssum[t][3]} + d1;
                                 const f32x2 q0 = d0 * d0 + (f32x2){ssq[t][0], ssq[t][1]}, q1 = d1 * d1 + (f32x2){ssq[t][2], ssq[t][3]};
@@ -760,7 +816,7 @@ __device__ __forceinline__ void conv_fwd_kernel(const chap_conv_params& P) {
                                 ssq[t][0] = q0.x; ssq[t][1] = q0.y; ssq[t][2] = q1.x; ssq[t][3] = q1.y;
                             }
                             if (CHAP_ABLATE & 8) { asm volatile("" :: "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3])); continue; }
-                            const unsigned oi = (unsigned)(row * orow + zw_off + ooff[t]);
+                            const unsigned oi = (unsigned)(row * orow + zw_off + oo);
                             if (valid) {
                                 if (P.out_f32) st4((float*)(ob + oi * 4u), v); else st4((T*)(obt + oi * (unsigned)sizeof(T)), v);
                             }
@@ -796,6 +852,7 @@ __device__ __forceinline__ void conv_fwd_kernel(const chap_conv_params& P) {
 
     CHAP_STAMP_P(4);
     if (do_stats) {
+        if constexpr (BCL) __syncthreads();                     // every wave is through with the bias / shift values in wave 3's rows
         // (the wave's row, conv_stats_row's layout, written in place: through the function the register allocation of some instances moves)
 #pragma unroll
         for (int t = 0; t < NT; ++t) {

@@ -14,7 +14,7 @@ BF, F32 = torch.bfloat16, torch.float32
 
 def planner():
     """request line -> dict of the plan (route, KC, NT, MR, cpar, ...), under the knobs of the environment at the time of the call"""
-    from tests.test_launch_plan_cpu import PROBE, ROOT, CSRC
+    from tests.plan_probe import PROBE, ROOT, CSRC
     d = tempfile.mkdtemp(prefix="plan_probe")
     open(os.path.join(d, "probe.cpp"), "w").write(PROBE)
     exe = os.path.join(d, "probe")
@@ -129,6 +129,11 @@ def run_cases():
                                    ("slab64", (3, 10, 14, 14), 64, {"CHAP_CONV_KPAR": "0"}), ("kpar128", (2, 10, 14, 14), 128, {"CHAP_CONV_KPAR": "1"})):
         conv("3d %s" % route, [lazy(shape[0], shape[1:], c, BF, chan_mul=True)], c, c, shape, shape[1:], BF, dims=3, knobs=knobs,
              route="kpar4" if route == "kpar128" else "generic")
+    # ---- the instances on staged weights with 64 output channels per block: 2D k2 s2 (two K chunks; 32 -> 128: two channel groups), the V-Net skip add on bricks
+    conv("k2s2 bf16 2D 64->64 staged", [lazy(2, (1, 30, 44), 64, BF)], 64, 64, (2, 1, 15, 22), (1, 30, 44), BF, ksize=2, stride=2)
+    conv("k2s2 bf16 2D 32->128 staged", [lazy(2, (1, 30, 44), 32, BF, keep=True)], 32, 128, (2, 1, 15, 22), (1, 30, 44), BF, ksize=2, stride=2)
+    conv("3d bricks add-combine 64+64 staged", [lazy(1, (10, 14, 30), 64, BF, chan_mul=True), lazy(1, (10, 14, 30), 64, BF, affine=False)], 64, 64, (1, 10, 14, 30),
+         (10, 14, 30), BF, dims=3, combine=1, knobs={"CHAP_CONV_KPAR": "0", "CHAP_CONV_MR": "4", "CHAP_CONV_NT": "2"})
     conv("3d bricks add-combine", [lazy(2, (12, 18, 30), 16, BF, chan_mul=True), lazy(2, (12, 18, 30), 16, BF, affine=False)], 16, 16, (2, 12, 18, 30), (12, 18, 30),
          BF, dims=3, combine=1, knobs={"CHAP_CONV_KPAR": "0"})
     # ---- wave-private (conv_wp_kernel): the parameter sets of test_conv_wave_private_2d
