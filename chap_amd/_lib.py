@@ -308,7 +308,12 @@ class AdamParams(C.Structure):                  # chap_adam_params
                 ("decoupled", _i32), ("grad_scale", _f32), ("zero_grad", _i32), ("n", _i64)]
 
 
-MONITOR_SLOTS, MONITOR_MAX_SCALARS, MONITOR_HDR = 512, 16, 2       # CHAP_MONITOR_* of include/chap_hip_monitor.h
+class TeacherConsistencyParams(C.Structure):    # chap_teacher_consistency_params of include/chap_hip_teacher.h
+    _fields_ = [("logits", _vp * 2), ("teacher", _vp * 2), ("dlogits", _vp * 2), ("loss", _vp), ("ws", _vp), ("gscale_dev", _vp),
+                ("gscale", _f32), ("accumulate", _i32), ("N", _i32), ("C", _i32), ("P", _i32)]
+
+
+MONITOR_SLOTS, MONITOR_MAX_SCALARS, MONITOR_HDR = 512, 16, 2      # CHAP_MONITOR_* of include/chap_hip_monitor.h
 
 
 class MonitorParams(C.Structure):
@@ -356,6 +361,9 @@ _SIGS_GUARD = {"chap_grad_norm": GradNormParams, "chap_sgd_guard_step": SgdGuard
 # points get their rows there (a test-only change) they stay out of that walk; _fn() below still looks the table up, so
 # call("chap_adam_step", ...) gets its argtypes like every other entry point.
 _OPTIM_SIGS = {"chap_adam_tick": AdamTickParams, "chap_adam_step": AdamParams}
+# the mean teacher's consistency term, declared in include/chap_hip_teacher.h (same calling convention): issued only by a step built with
+# teacher_consistency > 0.  Named like _OPTIM_SIGS and for the same reason.
+_TEACHER_SIGS = {"chap_teacher_consistency": TeacherConsistencyParams}
 _SIZE_FNS = {"chap_pack_size": PackParams, "chap_conv_c1_bwd_ws": ConvC1BwdParams, "chap_wgrad_ws": WgradParams,
              "chap_lcc_ws": LccParams, "chap_metrics_ws": MetricsParams}
 
@@ -406,9 +414,9 @@ def _fn(name):
             fn = getattr(L, name)
         except AttributeError:
             raise ChapError("libchap_hip.so does not export %s (stale build?)" % name)
-        if name in _SIGS or name in _SIGS_EXT or name in _SIGS_MONITOR or name in _SIGS_GUARD or name in _OPTIM_SIGS:
+        if name in _SIGS or name in _SIGS_EXT or name in _SIGS_MONITOR or name in _SIGS_GUARD or name in _OPTIM_SIGS or name in _TEACHER_SIGS:
             fn.restype, fn.argtypes = C.c_int, [C.POINTER(_SIGS.get(name) or _SIGS_EXT.get(name) or _SIGS_MONITOR.get(name) or _SIGS_GUARD.get(name)
-                                                          or _OPTIM_SIGS[name]), _vp]
+                                                          or _OPTIM_SIGS.get(name) or _TEACHER_SIGS[name]), _vp]
         else:
             fn.restype, fn.argtypes = _sz, [C.POINTER(_SIZE_FNS[name])]
         _bound[name] = fn

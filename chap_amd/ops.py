@@ -418,6 +418,30 @@ def kl_fwd_bwd(logits, targets, loss, dlogits=(None, None), gscale=1.0, gscale_d
     L.call("chap_kl_fwd_bwd", p, _stream())
 
 
+def teacher_consistency_ws_words():
+    return (1 + L.LOSS_SLOTS) * 2
+
+
+def teacher_consistency(logits, teacher, loss, dlogits=(None, None), gscale=1.0, gscale_dev=None, accumulate=False, ws=None):
+    """loss (1-elem fp32 tensor) = sum over the student's two heads of mean_{n,c,p} (softmax(logits[h]) - q)^2 with q the mean of the teacher's
+    two softmax outputs; dlogits[h] (or None) = gscale * (*gscale_dev) * d loss / d logits[h], added to what it holds with `accumulate`
+    (include/chap_hip_teacher.h).  `ws`: [1 + LOSS_SLOTS][2] fp32 per-block partials, allocated here when not given."""
+    p = L.TeacherConsistencyParams()
+    shape = logits[0].shape
+    for t in (logits[0], logits[1], teacher[0], teacher[1], dlogits[0], dlogits[1]):
+        if t is not None and (t.shape != shape or t.dtype != torch.float32 or not t.is_contiguous()):
+            raise ValueError("chap_amd teacher_consistency: every tensor must be contiguous fp32 of shape %s, got %s %s" % (tuple(shape), t.dtype, tuple(t.shape)))
+    if ws is None:
+        ws = L.hold_empty(teacher_consistency_ws_words(), dtype=torch.float32, device=logits[0].device)
+    elif ws.numel() < teacher_consistency_ws_words() or ws.dtype != torch.float32 or not ws.is_contiguous():
+        raise ValueError("chap_amd teacher_consistency: ws must hold %d contiguous fp32 words" % teacher_consistency_ws_words())
+    for h in range(2):
+        p.logits[h], p.teacher[h], p.dlogits[h] = logits[h].data_ptr(), teacher[h].data_ptr(), _p(dlogits[h])
+    p.loss, p.ws, p.gscale, p.gscale_dev, p.accumulate = loss.data_ptr(), ws.data_ptr(), gscale, _p(gscale_dev), int(bool(accumulate))
+    p.N, p.C, p.P = shape[0], shape[1], logits[0][0, 0].numel() if shape[0] > 0 else 0
+    L.call("chap_teacher_consistency", p, _stream())
+
+
 def l2_normalize(x, out, eps=1e-8):
     p = L.L2NormParams()
     ws = L.hold_empty(x.shape[0] * L.L2NORM_SLOTS, dtype=torch.float32, device=x.device)

@@ -32,7 +32,8 @@ def get_current_consistency_weight(epoch, args):            # train_ours_2D.py:3
 DEFAULT_ARGS = dict(base_lr=0.01, batch_size=24, labeled_bs=12, max_iterations=30000, num_classes=4,
                     consistency=1.0, consistency_rampup=50.0, noise_mag=10.0, epi=6.0, topk1=0.1,
                     adv_noise=True, adv_losstype="kl", vat_iters=1, vat_sign=False, nms=1,
-                    momentum=0.9, weight_decay=1e-4, dropout=False, comp_drop=False)
+                    momentum=0.9, weight_decay=1e-4, dropout=False, comp_drop=False,
+                    teacher_consistency=0.0, teacher_noise=0.1)
 
 
 def ema_alpha(global_step, decay):
@@ -236,6 +237,19 @@ def optimizer_line(args):
         name, args["base_lr"], b[0], b[1], args.get("adam_eps", 1e-8), args.get("weight_decay", 1e-4), "decoupled" if name == "adamw" else "L2")
 
 
+def check_teacher_consistency(args, have_teacher, who="chap_amd"):
+    """args['teacher_consistency'] (0 = off: the mean teacher is only averaged) and args['teacher_noise'].  The term needs a teacher to run; the
+    train() entries and ChapStep call this before anything is allocated or written."""
+    w, noise = float(args.get("teacher_consistency", 0.0)), float(args.get("teacher_noise", 0.1))
+    if not (math.isfinite(w) and w >= 0.0):
+        raise ValueError("%s: teacher_consistency=%r, need a finite weight >= 0" % (who, args.get("teacher_consistency")))
+    if w > 0.0 and not have_teacher:
+        raise ValueError("%s: teacher_consistency=%g needs the mean teacher (mean_teacher=True / ChapStep(teacher=...)): its predictions are the target" % (who, w))
+    if w > 0.0 and not (math.isfinite(noise) and noise >= 0.0):
+        raise ValueError("%s: teacher_noise=%r, need a finite magnitude >= 0" % (who, args.get("teacher_noise")))
+    return w
+
+
 def build_optimizer(model, args):
     """args['optimizer']: 'sgd' (default) -> FusedSGD(base_lr, momentum, weight_decay); 'adam' / 'adamw' -> FusedAdamW(base_lr, betas, adam_eps,
     weight_decay) with L2 / decoupled weight decay."""
@@ -425,6 +439,8 @@ class ChapStep:
         a = dict(DEFAULT_ARGS)
         a.update(args or {})
         self.args, self.model = a, model
+        # weight of the mean teacher's consistency term (0: the teacher is averaged and never run, the step is launch for launch the one without the argument)
+        self.teacher_w = check_teacher_consistency(a, teacher is not None, "chap_amd %s" % type(self).__name__)
         self.opt = optimizer or build_optimizer(model, a)
         self.adv_loss = VAT2d(xi=a["noise_mag"], epi=a["epi"], num_classes=a["num_classes"], ip=a["vat_iters"], sign=a["vat_sign"])
         dev = self.opt.lr_dev.device
@@ -505,7 +521,8 @@ class ChapStep:
     def _attach_teacher(self, teacher):
         """`teacher`: a second instance of the student's class, create_model(ema=True) (:238-245).  Its parameters never require grad (:243-244); its
         flat parameter buffer is what the optimizer kernel averages the student's weights into, with the coefficients in words 8-9 of the
-        schedule block.  It is never run by the iteration: evaluate it after sync_teacher_stats()."""
+        schedule block.  With args['teacher_consistency'] > 0 pass B runs it on a noised copy of its input and pulls the student towards its
+        prediction (_teacher_pass); otherwise the iteration never runs it.  To evaluate it, call sync_teacher_stats() first."""
         model = self.model
         if not isinstance(self.opt, FusedOptimizer):
             raise ValueError("chap_amd ChapStep: a mean teacher needs the fused optimizer (FusedSGD): its average is part of that kernel")
@@ -672,6 +689,8 @@ class ChapStep:
                     losses = self._phase_b(ctx)
                 vat_loss = self._phase_v(ctx)
         out = {"mix_losses": losses, "vat_loss": vat_loss}
+        if self.teacher_w > 0:
+            out["teacher_loss"] = ctx["teacher_loss"]
         if self.args["dropout"]:        # (behind _decoder_fork's join: the fp branch never forks its second decoder under capture)
             out["fp_losses"] = self._fp_branch(ctx["uimg_ab"], ctx["pseudo_outputs1"], ctx["pseudo_outputs2"], ctx["inject"], None)
         if self.monitor is not None:    # behind the join of pass B's stream above: both accumulate launches and every loss word are complete
@@ -738,6 +757,11 @@ class ChapStep:
         #  order -- see Executor.forward -- together with stream handles repeating in PyTorch's pool, see ChapStep.__init__.)
         pre = self._pre if (self.concurrent and a["adv_noise"] and a.get("vat_early", True)) else None
         model.prepare_weights()                  # before the streams fork: every pass of the iteration reads the same packed copies
+        if self.teacher_w > 0:                   # the optimizer launch rewrote the teacher's flat buffer: its packed copies too, here and not on pass B's stream
+            self.teacher.set_compute_dtype(model.compute_dtype)
+            if torch.cuda.is_current_stream_capturing():
+                self.teacher.mark_params_dirty()        # the pack launch is a node of every captured iteration, whatever was packed before the capture
+            self.teacher.prepare_weights()
         if a["adv_noise"]:
             if pre is not None:
                 # The early pass runs on its own stream beside pass A and is issued in FRONT of it (round 4 tried issuing it between pass A's encoder and
@@ -797,6 +821,8 @@ class ChapStep:
         plab_a1, plab_b1 = plab1[:usub], plab1[usub:]
         plab_a2, plab_b2 = plab2[:usub], plab2[usub:]
         out_mix1, out_mix2 = model(net_input_mix, drop_masks=inject.get("drop_B"))
+        # the teacher's pass behind the student's (whose dropout seeds are the ones it draws without a teacher), on this stream
+        tch = self._teacher_pass(net_input_mix, inject) if self.teacher_w > 0 else None
         d1, d2 = torch.empty_like(out_mix1), torch.empty_like(out_mix2)
         terms = (  # (logits, dlogits, img_l, patch_l, unlab)
             (out_mix1[lsub:], d1[lsub:], plab_a2, lab_a, True),      # mix_loss1: out_unl1
@@ -835,6 +861,12 @@ class ChapStep:
             else:
                 ops.mix_loss_bwd(lg, img_l, patch_l, loss_mask, iw, pw, acc, dl)
             losses.append(loss3)
+        if tch is not None:
+            # softmax-MSE of both heads against the teacher's ensemble, weighted cw * teacher_consistency; its gradient is added to what mix_loss_bwd
+            # has just written -- with `split` to the e set: the term is unsupervised (loss_u) -- and the backward below carries it
+            ctx["teacher_loss"] = torch.empty(1, dtype=torch.float32, device=out_mix1.device)
+            ops.teacher_consistency((out_mix1, out_mix2), tch, ctx["teacher_loss"], (e1, e2) if split else (d1, d2), gscale=self.teacher_w,
+                                    gscale_dev=self.cw_dev, accumulate=True)
         if not split:
             torch.autograd.backward([out_mix1, out_mix2], [d1, d2])
             return losses
@@ -852,6 +884,32 @@ class ChapStep:
         ops.perturb(b0, g_l, b0, 1.0)
         ops.perturb(b0, g_u, b0, 1.0)
         return losses
+
+    def _teacher_pass(self, x, inject):
+        """The mean teacher's prediction on x + u, u uniform in [-teacher_noise, teacher_noise) (Tarvainen and Valpola; the public code adds a clipped
+        Gaussian, DESIGN.md "Mean teacher"), on the current stream and without gradients: nothing is saved.  BatchNorm normalises with the batch's
+        own statistics (the public code never puts its ema_model into eval()) and updates no running buffer; the shift of the statistics' sums is
+        the iteration's snapshot of the STUDENT's running means, so the teacher's own never-updated ones play no role.  The noise seed and the
+        seeds of the dropout sites come from the student's generator, in program order: one stream, one checkpointed state."""
+        model, t = self.model, self.teacher
+        noise = float(self.args["teacher_noise"])
+        with torch.no_grad():
+            x_t = x
+            if noise > 0:
+                u = inject.get("teacher_u")             # (tests: a static noise tensor, as `d0` is the VAT branch's)
+                if u is None:
+                    u = torch.empty_like(x)
+                    ops.rand_uniform(u, model._rng.next_seed(), -noise, noise, seed_dev=model._rng.seed_dev)
+                x_t = torch.empty_like(x)
+                ops.perturb(x, u, x_t, 1.0)
+            t._ensure_flat()
+            old = (t._rng, t._shift_hold, t.training)
+            t._rng, t._shift_hold, t.training = model._rng, model._shift_hold, True
+            try:
+                t1, t2 = t(x_t, update_stats=False, drop_masks=inject.get("drop_T"))
+            finally:
+                t._rng, t._shift_hold, t.training = old
+        return t1, t2
 
     def _phase_v(self, ctx):
         a = self.args
@@ -980,6 +1038,8 @@ class ChapStep:
             with self._decoder_fork(torch.cuda.current_stream()):
                 vat_loss = self._phase_v(ctx)
             out = {"mix_losses": losses, "vat_loss": vat_loss}
+            if self.teacher_w > 0:
+                out["teacher_loss"] = ctx["teacher_loss"]
             if self.args["dropout"]:    # (behind _decoder_fork's join, as in _iteration: no fork)
                 out["fp_losses"] = self._fp_branch(ctx["uimg_ab"], ctx["pseudo_outputs1"], ctx["pseudo_outputs2"], ctx["inject"], None)
         stack.close()
@@ -1075,6 +1135,11 @@ class AblationStep(ChapStep):
     With a monitor: the full-batch forward is scored with n_first = labeled_bs, acc_conf_analysis's split (train_ours_2D.py:157-158)."""
 
     MONITOR_LAYOUT = "ablation"
+
+    def __init__(self, model, args=None, *pos, **kw):
+        if float((args or {}).get("teacher_consistency", 0.0)) > 0:
+            raise ValueError("chap_amd AblationStep: teacher_consistency=%g: the mean teacher's consistency term exists in ChapStep's pass B only" % float(args["teacher_consistency"]))
+        super().__init__(model, args, *pos, **kw)
 
     def _iteration(self, volume_batch, label_batch, inject=None, update=True):
         a, model = self.args, self.model
