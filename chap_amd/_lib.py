@@ -313,6 +313,19 @@ class TeacherConsistencyParams(C.Structure):    # chap_teacher_consistency_param
                 ("gscale", _f32), ("accumulate", _i32), ("N", _i32), ("C", _i32), ("P", _i32)]
 
 
+UNCERTAINTY_MAX_T = 8            # CHAP_UNCERTAINTY_MAX_T of include/chap_hip_uncertainty.h
+
+
+class TeacherUncertaintyParams(C.Structure):    # chap_teacher_uncertainty_params of include/chap_hip_uncertainty.h
+    _fields_ = [("teacher", (_vp * 2) * UNCERTAINTY_MAX_T), ("mask", _vp), ("entropy", _vp), ("count", _vp), ("ws", _vp), ("threshold_dev", _vp),
+                ("threshold", _f32), ("T", _i32), ("N", _i32), ("C", _i32), ("P", _i32)]
+
+
+class TeacherConsistencyMaskedParams(C.Structure):      # chap_teacher_consistency_masked_params
+    _fields_ = [("logits", _vp * 2), ("teacher", _vp * 2), ("mask", _vp), ("count", _vp), ("dlogits", _vp * 2), ("loss", _vp), ("ws", _vp),
+                ("gscale_dev", _vp), ("gscale", _f32), ("accumulate", _i32), ("N", _i32), ("C", _i32), ("P", _i32)]
+
+
 MONITOR_SLOTS, MONITOR_MAX_SCALARS, MONITOR_HDR = 512, 16, 2      # CHAP_MONITOR_* of include/chap_hip_monitor.h
 
 
@@ -364,6 +377,9 @@ _OPTIM_SIGS = {"chap_adam_tick": AdamTickParams, "chap_adam_step": AdamParams}
 # the mean teacher's consistency term, declared in include/chap_hip_teacher.h (same calling convention): issued only by a step built with
 # teacher_consistency > 0.  Named like _OPTIM_SIGS and for the same reason.
 _TEACHER_SIGS = {"chap_teacher_consistency": TeacherConsistencyParams}
+# its uncertainty-aware form, declared in include/chap_hip_uncertainty.h (same calling convention): issued only by a step built with
+# teacher_uncertainty > 0.  Named like _OPTIM_SIGS and for the same reason.
+_UNCERTAINTY_SIGS = {"chap_teacher_uncertainty": TeacherUncertaintyParams, "chap_teacher_consistency_masked": TeacherConsistencyMaskedParams}
 _SIZE_FNS = {"chap_pack_size": PackParams, "chap_conv_c1_bwd_ws": ConvC1BwdParams, "chap_wgrad_ws": WgradParams,
              "chap_lcc_ws": LccParams, "chap_metrics_ws": MetricsParams}
 
@@ -414,9 +430,9 @@ def _fn(name):
             fn = getattr(L, name)
         except AttributeError:
             raise ChapError("libchap_hip.so does not export %s (stale build?)" % name)
-        if name in _SIGS or name in _SIGS_EXT or name in _SIGS_MONITOR or name in _SIGS_GUARD or name in _OPTIM_SIGS or name in _TEACHER_SIGS:
+        if name in _SIGS or name in _SIGS_EXT or name in _SIGS_MONITOR or name in _SIGS_GUARD or name in _OPTIM_SIGS or name in _TEACHER_SIGS or name in _UNCERTAINTY_SIGS:
             fn.restype, fn.argtypes = C.c_int, [C.POINTER(_SIGS.get(name) or _SIGS_EXT.get(name) or _SIGS_MONITOR.get(name) or _SIGS_GUARD.get(name)
-                                                          or _OPTIM_SIGS.get(name) or _TEACHER_SIGS[name]), _vp]
+                                                          or _OPTIM_SIGS.get(name) or _TEACHER_SIGS.get(name) or _UNCERTAINTY_SIGS[name]), _vp]
         else:
             fn.restype, fn.argtypes = _sz, [C.POINTER(_SIZE_FNS[name])]
         _bound[name] = fn

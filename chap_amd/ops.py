@@ -442,6 +442,69 @@ def teacher_consistency(logits, teacher, loss, dlogits=(None, None), gscale=1.0,
     L.call("chap_teacher_consistency", p, _stream())
 
 
+def teacher_uncertainty_ws_words():
+    return 1 + L.LOSS_SLOTS
+
+
+def teacher_uncertainty(passes, threshold=0.0, threshold_dev=None, want_entropy=False, ws=None):
+    """`passes`: T = 1..8 pairs (head 1, head 2) of teacher logits [N][C][...].  -> (mask uint8 [N][...], count int64 [1][, entropy fp32 [N][...]]):
+    mask = entropy of the mean of the 2T softmax outputs < threshold (`threshold_dev`, a 1-elem fp32 tensor, replaces the host value), count
+    its exact sum (include/chap_hip_uncertainty.h).  `ws`: [1 + LOSS_SLOTS] int64 per-block partials, allocated here when not given."""
+    p = L.TeacherUncertaintyParams()
+    T = len(passes)
+    if not 1 <= T <= L.UNCERTAINTY_MAX_T:
+        raise ValueError("chap_amd teacher_uncertainty: %d passes, need 1..%d" % (T, L.UNCERTAINTY_MAX_T))
+    shape = passes[0][0].shape
+    for k, pair in enumerate(passes):
+        if len(pair) != 2:
+            raise ValueError("chap_amd teacher_uncertainty: pass %d has %d heads, need 2" % (k, len(pair)))
+        for h, t in enumerate(pair):
+            if t.shape != shape or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError("chap_amd teacher_uncertainty: every tensor must be contiguous fp32 of shape %s, got %s %s" % (tuple(shape), t.dtype, tuple(t.shape)))
+            p.teacher[k][h] = t.data_ptr()
+    if threshold_dev is not None and (threshold_dev.dtype != torch.float32 or threshold_dev.numel() != 1):
+        raise ValueError("chap_amd teacher_uncertainty: threshold_dev must be one fp32 word")
+    dev = passes[0][0].device
+    if ws is None:
+        ws = L.hold_empty(teacher_uncertainty_ws_words(), dtype=torch.int64, device=dev)
+    elif ws.numel() < teacher_uncertainty_ws_words() or ws.dtype != torch.int64 or not ws.is_contiguous():
+        raise ValueError("chap_amd teacher_uncertainty: ws must hold %d contiguous int64 words" % teacher_uncertainty_ws_words())
+    sp = (shape[0],) + tuple(shape[2:])
+    mask = torch.empty(sp, dtype=torch.uint8, device=dev)
+    count = torch.empty(1, dtype=torch.int64, device=dev)
+    entropy = torch.empty(sp, dtype=torch.float32, device=dev) if want_entropy else None
+    p.mask, p.entropy, p.count, p.ws = mask.data_ptr(), _p(entropy), count.data_ptr(), ws.data_ptr()
+    p.threshold, p.threshold_dev, p.T = float(threshold), _p(threshold_dev), T
+    p.N, p.C, p.P = shape[0], shape[1], passes[0][0][0, 0].numel() if shape[0] > 0 else 0
+    L.call("chap_teacher_uncertainty", p, _stream())
+    return (mask, count, entropy) if want_entropy else (mask, count)
+
+
+def teacher_consistency_masked(logits, teacher, mask, count, loss, dlogits=(None, None), gscale=1.0, gscale_dev=None, accumulate=False, ws=None):
+    """teacher_consistency counted over the pixels with mask = 1 only and normalised by C * count (`count`: a 1-elem int64 device tensor, the
+    number of ones in `mask`): loss = sum_h sum m e_h^2 / (C count + 1e-16); where mask = 0 the gradient is exactly 0 -- with `accumulate` the
+    element keeps what it holds (include/chap_hip_uncertainty.h).  `ws`: [1 + LOSS_SLOTS][2] fp32, allocated here when not given."""
+    p = L.TeacherConsistencyMaskedParams()
+    shape = logits[0].shape
+    for t in (logits[0], logits[1], teacher[0], teacher[1], dlogits[0], dlogits[1]):
+        if t is not None and (t.shape != shape or t.dtype != torch.float32 or not t.is_contiguous()):
+            raise ValueError("chap_amd teacher_consistency_masked: every tensor must be contiguous fp32 of shape %s, got %s %s" % (tuple(shape), t.dtype, tuple(t.shape)))
+    if mask.dtype != torch.uint8 or not mask.is_contiguous() or tuple(mask.shape) != (shape[0],) + tuple(shape[2:]):
+        raise ValueError("chap_amd teacher_consistency_masked: mask must be contiguous uint8 of shape %s, got %s %s" % ((shape[0],) + tuple(shape[2:]), mask.dtype, tuple(mask.shape)))
+    if count.dtype != torch.int64 or count.numel() != 1:
+        raise ValueError("chap_amd teacher_consistency_masked: count must be one int64 word")
+    if ws is None:
+        ws = L.hold_empty(teacher_consistency_ws_words(), dtype=torch.float32, device=logits[0].device)
+    elif ws.numel() < teacher_consistency_ws_words() or ws.dtype != torch.float32 or not ws.is_contiguous():
+        raise ValueError("chap_amd teacher_consistency_masked: ws must hold %d contiguous fp32 words" % teacher_consistency_ws_words())
+    for h in range(2):
+        p.logits[h], p.teacher[h], p.dlogits[h] = logits[h].data_ptr(), teacher[h].data_ptr(), _p(dlogits[h])
+    p.mask, p.count = mask.data_ptr(), count.data_ptr()
+    p.loss, p.ws, p.gscale, p.gscale_dev, p.accumulate = loss.data_ptr(), ws.data_ptr(), gscale, _p(gscale_dev), int(bool(accumulate))
+    p.N, p.C, p.P = shape[0], shape[1], logits[0][0, 0].numel() if shape[0] > 0 else 0
+    L.call("chap_teacher_consistency_masked", p, _stream())
+
+
 def l2_normalize(x, out, eps=1e-8):
     p = L.L2NormParams()
     ws = L.hold_empty(x.shape[0] * L.L2NORM_SLOTS, dtype=torch.float32, device=x.device)

@@ -33,7 +33,8 @@ DEFAULT_ARGS = dict(base_lr=0.01, batch_size=24, labeled_bs=12, max_iterations=3
                     consistency=1.0, consistency_rampup=50.0, noise_mag=10.0, epi=6.0, topk1=0.1,
                     adv_noise=True, adv_losstype="kl", vat_iters=1, vat_sign=False, nms=1,
                     momentum=0.9, weight_decay=1e-4, dropout=False, comp_drop=False,
-                    teacher_consistency=0.0, teacher_noise=0.1)
+                    teacher_consistency=0.0, teacher_noise=0.1,
+                    teacher_uncertainty=0, uncertainty_threshold=(0.75, 1.0))
 
 
 def ema_alpha(global_step, decay):
@@ -250,6 +251,35 @@ def check_teacher_consistency(args, have_teacher, who="chap_amd"):
     return w
 
 
+def check_teacher_uncertainty(args, who="chap_amd"):
+    """args['teacher_uncertainty'] (0 = off, or T = 1..8 noisy teacher passes whose mean prediction's entropy masks the consistency term) and
+    args['uncertainty_threshold'] = (lo, hi), fractions of ln C with 0 < lo <= hi.  T > 0 needs the term itself (teacher_consistency > 0, hence
+    the teacher).  Called where check_teacher_consistency is, before anything is allocated or written.  -> T"""
+    T = args.get("teacher_uncertainty", 0)
+    if isinstance(T, bool) or not isinstance(T, (int, np.integer)) or not 0 <= T <= 8:
+        raise ValueError("%s: teacher_uncertainty=%r, need 0 (off) or the number of noisy teacher passes T = 1..8" % (who, T))
+    T = int(T)
+    if T == 0:
+        return 0
+    if not float(args.get("teacher_consistency", 0.0)) > 0.0:
+        raise ValueError("%s: teacher_uncertainty=%d needs teacher_consistency > 0: it masks that term" % (who, T))
+    thr = args.get("uncertainty_threshold", (0.75, 1.0))
+    try:
+        lo, hi = (float(v) for v in thr)
+    except (TypeError, ValueError):
+        raise ValueError("%s: uncertainty_threshold=%r, need two fractions (lo, hi) of ln C" % (who, thr))
+    if not (math.isfinite(lo) and math.isfinite(hi) and 0.0 < lo <= hi):
+        raise ValueError("%s: uncertainty_threshold=%r, need finite fractions of ln C with 0 < lo <= hi" % (who, thr))
+    return T
+
+
+def uncertainty_threshold(iter_num, args):
+    """thr(iter) = (lo + (hi - lo) * sigmoid_rampup(iter, max_iterations)) * ln C: the uncertainty-aware mean teacher's
+    (0.75 + 0.25 * ramp) * ln 2, for C classes."""
+    lo, hi = (float(v) for v in args.get("uncertainty_threshold", (0.75, 1.0)))
+    return (lo + (hi - lo) * sigmoid_rampup(iter_num, args["max_iterations"])) * math.log(args["num_classes"])
+
+
 def build_optimizer(model, args):
     """args['optimizer']: 'sgd' (default) -> FusedSGD(base_lr, momentum, weight_decay); 'adam' / 'adamw' -> FusedAdamW(base_lr, betas, adam_eps,
     weight_decay) with L2 / decoupled weight decay."""
@@ -441,13 +471,16 @@ class ChapStep:
         self.args, self.model = a, model
         # weight of the mean teacher's consistency term (0: the teacher is averaged and never run, the step is launch for launch the one without the argument)
         self.teacher_w = check_teacher_consistency(a, teacher is not None, "chap_amd %s" % type(self).__name__)
+        # T noisy teacher passes behind the term's entropy mask (0: the plain term, launch for launch)
+        self.teacher_T = check_teacher_uncertainty(a, "chap_amd %s" % type(self).__name__)
         self.opt = optimizer or build_optimizer(model, a)
         self.adv_loss = VAT2d(xi=a["noise_mag"], epi=a["epi"], num_classes=a["num_classes"], ip=a["vat_iters"], sign=a["vat_sign"])
         dev = self.opt.lr_dev.device
         self.dims = getattr(model, "dims", 2)
         # host-scheduled values of an iteration in ONE device word block -> one host-to-device copy per step:
         # [BCP box: 4 / 6 int32 | consistency weight f32 | learning rate f32], and with a mean teacher [| a f32 | b f32] of its average behind them,
-        # and with a monitor [| ring slot int32 | iteration int32] of the row its finalize kernel writes behind those
+        # and with a monitor [| ring slot int32 | iteration int32] of the row its finalize kernel writes behind those, and with teacher_uncertainty
+        # [| entropy threshold f32] behind everything else
         nbox = 4 if self.dims == 2 else 6
         self.teacher = teacher
         nsched = 8 if teacher is None else 10
@@ -458,11 +491,16 @@ class ChapStep:
             monitor.scalar_layout = self.MONITOR_LAYOUT
             self._mon_at = nsched
             nsched += 2
+        if self.teacher_T > 0:      # [| entropy threshold f32] of the uncertainty mask, appended: no other word moves
+            self._thr_at = nsched
+            nsched += 1
         self._sched = torch.zeros(nsched, dtype=torch.int32, device=dev)
         self._sched_pin = [torch.empty(nsched, dtype=torch.int32).pin_memory() for _ in range(4)]      # host side of the schedule block (see _upload_sched)
         self._sched_ev, self._sched_k = [None] * 4, 0
         self.box = self._sched[:nbox]
         self.cw_dev = self._sched[6:7].view(torch.float32)
+        self.teacher_pixels = 0
+        self.thr_dev = self._sched[self._thr_at:self._thr_at + 1].view(torch.float32) if self.teacher_T > 0 else None
         if isinstance(self.opt, FusedOptimizer):                 # the optimizer reads its lr from the same block
             self._sched[7:8].view(torch.float32).copy_(self.opt.lr_dev)
             self.opt.lr_dev = self._sched[7:8].view(torch.float32)
@@ -574,6 +612,8 @@ class ChapStep:
             vals += [f2i(c) for c in ema_coefficients(self.iter_num, self.opt.ema_decay)]
         if self.monitor is not None:            # the row of this iteration: its ring slot, and the number the reference's log line prints (iter_num + 1, train_ours_2D.py:385,404-405)
             vals += [self.monitor.next_slot(), self.iter_num + 1]
+        if self.teacher_T > 0:
+            vals += [f2i(uncertainty_threshold(self.iter_num, self.args))]
         # Through a small ring of PINNED host blocks, asynchronously: a plain `copy_` from pageable memory synchronises the stream,
         # i.e. the host would wait for the previous iteration to drain before it even starts launching the next one (the GPU then
         # idles while the graph's first nodes are being submitted: ~0.5 ms of gaps at the head of every replay in the kernel trace).
@@ -691,6 +731,8 @@ class ChapStep:
         out = {"mix_losses": losses, "vat_loss": vat_loss}
         if self.teacher_w > 0:
             out["teacher_loss"] = ctx["teacher_loss"]
+        if self.teacher_T > 0:
+            out["teacher_certain"] = ctx["teacher_certain"]
         if self.args["dropout"]:        # (behind _decoder_fork's join: the fp branch never forks its second decoder under capture)
             out["fp_losses"] = self._fp_branch(ctx["uimg_ab"], ctx["pseudo_outputs1"], ctx["pseudo_outputs2"], ctx["inject"], None)
         if self.monitor is not None:    # behind the join of pass B's stream above: both accumulate launches and every loss word are complete
@@ -823,6 +865,8 @@ class ChapStep:
         out_mix1, out_mix2 = model(net_input_mix, drop_masks=inject.get("drop_B"))
         # the teacher's pass behind the student's (whose dropout seeds are the ones it draws without a teacher), on this stream
         tch = self._teacher_pass(net_input_mix, inject) if self.teacher_w > 0 else None
+        # with teacher_uncertainty = T: pass 0 above stays the target, T - 1 more passes follow, each under its own noise draw (and dropout seeds)
+        tpasses = [tch] + [self._teacher_pass(net_input_mix, inject, k) for k in range(1, self.teacher_T)] if self.teacher_T > 0 else None
         d1, d2 = torch.empty_like(out_mix1), torch.empty_like(out_mix2)
         terms = (  # (logits, dlogits, img_l, patch_l, unlab)
             (out_mix1[lsub:], d1[lsub:], plab_a2, lab_a, True),      # mix_loss1: out_unl1
@@ -865,8 +909,17 @@ class ChapStep:
             # softmax-MSE of both heads against the teacher's ensemble, weighted cw * teacher_consistency; its gradient is added to what mix_loss_bwd
             # has just written -- with `split` to the e set: the term is unsupervised (loss_u) -- and the backward below carries it
             ctx["teacher_loss"] = torch.empty(1, dtype=torch.float32, device=out_mix1.device)
-            ops.teacher_consistency((out_mix1, out_mix2), tch, ctx["teacher_loss"], (e1, e2) if split else (d1, d2), gscale=self.teacher_w,
-                                    gscale_dev=self.cw_dev, accumulate=True)
+            if tpasses is None:
+                ops.teacher_consistency((out_mix1, out_mix2), tch, ctx["teacher_loss"], (e1, e2) if split else (d1, d2), gscale=self.teacher_w,
+                                        gscale_dev=self.cw_dev, accumulate=True)
+            else:
+                # the term only where the entropy of the T passes' mean prediction lies under the scheduled threshold, normalised by the count
+                # of such pixels (this rank's own): a masked-out pixel's gradient stays what mix_loss_bwd wrote
+                certain, count = ops.teacher_uncertainty(tpasses, threshold_dev=self.thr_dev)
+                ctx["teacher_certain"] = count
+                self.teacher_pixels = certain.numel()       # N * P of the term: count / teacher_pixels is the certain share
+                ops.teacher_consistency_masked((out_mix1, out_mix2), tch, certain, count, ctx["teacher_loss"], (e1, e2) if split else (d1, d2),
+                                               gscale=self.teacher_w, gscale_dev=self.cw_dev, accumulate=True)
         if not split:
             torch.autograd.backward([out_mix1, out_mix2], [d1, d2])
             return losses
@@ -885,18 +938,21 @@ class ChapStep:
         ops.perturb(b0, g_u, b0, 1.0)
         return losses
 
-    def _teacher_pass(self, x, inject):
+    def _teacher_pass(self, x, inject, k=0):
         """The mean teacher's prediction on x + u, u uniform in [-teacher_noise, teacher_noise) (Tarvainen and Valpola; the public code adds a clipped
         Gaussian, DESIGN.md "Mean teacher"), on the current stream and without gradients: nothing is saved.  BatchNorm normalises with the batch's
         own statistics (the public code never puts its ema_model into eval()) and updates no running buffer; the shift of the statistics' sums is
         the iteration's snapshot of the STUDENT's running means, so the teacher's own never-updated ones play no role.  The noise seed and the
-        seeds of the dropout sites come from the student's generator, in program order: one stream, one checkpointed state."""
+        seeds of the dropout sites come from the student's generator, in program order: one stream, one checkpointed state.  `k`: which of the
+        teacher_uncertainty passes this is (0: the target's, the only one of the plain term); every pass draws its own noise."""
         model, t = self.model, self.teacher
         noise = float(self.args["teacher_noise"])
         with torch.no_grad():
             x_t = x
             if noise > 0:
-                u = inject.get("teacher_u")             # (tests: a static noise tensor, as `d0` is the VAT branch's)
+                u = inject.get("teacher_u")             # (tests: a static noise tensor, as `d0` is the VAT branch's; a list: one per pass)
+                if isinstance(u, (list, tuple)):
+                    u = u[k]
                 if u is None:
                     u = torch.empty_like(x)
                     ops.rand_uniform(u, model._rng.next_seed(), -noise, noise, seed_dev=model._rng.seed_dev)
@@ -1040,6 +1096,8 @@ class ChapStep:
             out = {"mix_losses": losses, "vat_loss": vat_loss}
             if self.teacher_w > 0:
                 out["teacher_loss"] = ctx["teacher_loss"]
+            if self.teacher_T > 0:
+                out["teacher_certain"] = ctx["teacher_certain"]
             if self.args["dropout"]:    # (behind _decoder_fork's join, as in _iteration: no fork)
                 out["fp_losses"] = self._fp_branch(ctx["uimg_ab"], ctx["pseudo_outputs1"], ctx["pseudo_outputs2"], ctx["inject"], None)
         stack.close()
@@ -1139,6 +1197,8 @@ class AblationStep(ChapStep):
     def __init__(self, model, args=None, *pos, **kw):
         if float((args or {}).get("teacher_consistency", 0.0)) > 0:
             raise ValueError("chap_amd AblationStep: teacher_consistency=%g: the mean teacher's consistency term exists in ChapStep's pass B only" % float(args["teacher_consistency"]))
+        if (args or {}).get("teacher_uncertainty", 0):
+            raise ValueError("chap_amd AblationStep: teacher_uncertainty=%r: the mean teacher's consistency term exists in ChapStep's pass B only" % (args["teacher_uncertainty"],))
         super().__init__(model, args, *pos, **kw)
 
     def _iteration(self, volume_batch, label_batch, inject=None, update=True):

@@ -34,7 +34,7 @@ from .guard import StepGuard, check_finite_before_save, flush_to_run as flush_gu
 from .monitor import StepMonitor
 from .networks.net_factory import net_factory
 from .synthetic import synthetic_batch
-from .train import DEFAULT_ARGS, ChapStep, build_teacher, check_num_classes, check_optimizer, check_teacher_consistency, optimizer_line
+from .train import DEFAULT_ARGS, ChapStep, build_teacher, check_num_classes, check_optimizer, check_teacher_consistency, check_teacher_uncertainty, optimizer_line, uncertainty_threshold
 
 FLAG_DEFAULTS = dict(DEFAULT_ARGS, model="dualdecoder", decoder_type="mcnet", gpu=0, seed=1337, image_size=[256, 256],
                      val_interval=200, labeled_num=7, use_graph=True,          # train_ours_2D.py:469-526
@@ -60,6 +60,7 @@ def train(args, snapshot_path):
     check_num_classes(a["num_classes"], "chap_amd.train_ours_2D")
     check_optimizer(a["optimizer"], "chap_amd.train_ours_2D")
     check_teacher_consistency(a, bool(a["mean_teacher"]), "chap_amd.train_ours_2D")        # before a directory or a file is made
+    check_teacher_uncertainty(a, "chap_amd.train_ours_2D")
     ctx = init_rank(a)                          # the plain single process unless args["data_parallel"]
     log = logging.getLogger("chap_amd.train")
     log.setLevel(logging.INFO)
@@ -158,7 +159,11 @@ def _run(a, snapshot_path, ctx, log):
         if it % 50 == 0:                                                         # (:404 logs every iteration: a host sync each)
             log.info("iteration %d : bcp loss : %f vat loss : %f" % (it, sum(float(l[2]) for l in out["mix_losses"]), float(out["vat_loss"])))
         if "teacher_loss" in out and (it % 50 == 0 or it >= a["max_iterations"]):      # only with teacher_consistency > 0 (the default run's log is what it always was); the last iteration closes the record
-            log.info("iteration %d : teacher loss : %f" % (it, float(out["teacher_loss"])))
+            if "teacher_certain" in out:       # teacher_uncertainty > 0: the share of pixels the term counted, and the entropy threshold of this iteration
+                log.info("iteration %d : teacher loss : %f : certain share : %f : entropy threshold : %f" % (
+                    it, float(out["teacher_loss"]), float(out["teacher_certain"]) / step.teacher_pixels, uncertainty_threshold(it - 1, a)))
+            else:
+                log.info("iteration %d : teacher loss : %f" % (it, float(out["teacher_loss"])))
         if it > 0 and it % a["val_interval"] == 0:                               # :407-456
             sync_for_validation(ctx, step)       # (data-parallel) replicas equal, else raise; rank 0's BatchNorm statistics into every replica
             model.eval()

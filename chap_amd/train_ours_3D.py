@@ -32,7 +32,7 @@ from .networks.vnet import DualDecoder3d, VNet
 from .synthetic import synthetic_batch_3d
 from . import metrics
 from . import test_3d_patch as T3P
-from .train import DEFAULT_ARGS, ChapStep, build_teacher, check_num_classes, check_optimizer, check_teacher_consistency, optimizer_line
+from .train import DEFAULT_ARGS, ChapStep, build_teacher, check_num_classes, check_optimizer, check_teacher_consistency, check_teacher_uncertainty, optimizer_line, uncertainty_threshold
 
 FLAG_DEFAULTS = dict(DEFAULT_ARGS, model="dualdecoder", num_classes=2, patch_size=[112, 112, 80], batch_size=4, labeled_bs=2,
                      stride_xy=18, stride_z=4, val_interval=200, use_graph=True, gpu=0, seed=1337,
@@ -70,6 +70,7 @@ def train(args, snapshot_path):
     check_num_classes(a["num_classes"], "chap_amd.train_ours_3D")
     check_optimizer(a["optimizer"], "chap_amd.train_ours_3D")
     check_teacher_consistency(a, bool(a["mean_teacher"]), "chap_amd.train_ours_3D")        # before a directory or a file is made
+    check_teacher_uncertainty(a, "chap_amd.train_ours_3D")
     ctx = init_rank(a)                          # the plain single process unless args["data_parallel"]
     log = logging.getLogger("chap_amd.train3d")
     log.setLevel(logging.INFO)
@@ -167,7 +168,11 @@ def train(args, snapshot_path):
             if it % 50 == 0:
                 log.info("iteration %d : bcp loss : %f vat loss : %f" % (it, sum(float(l[2]) for l in out["mix_losses"]), float(out["vat_loss"])))
             if "teacher_loss" in out and (it % 50 == 0 or it >= a["max_iterations"]):      # only with teacher_consistency > 0 (the default run's log is what it always was); the last iteration closes the record
-                log.info("iteration %d : teacher loss : %f" % (it, float(out["teacher_loss"])))
+                if "teacher_certain" in out:       # teacher_uncertainty > 0: the share of pixels the term counted, and the entropy threshold of this iteration
+                    log.info("iteration %d : teacher loss : %f : certain share : %f : entropy threshold : %f" % (
+                        it, float(out["teacher_loss"]), float(out["teacher_certain"]) / step.teacher_pixels, uncertainty_threshold(it - 1, a)))
+                else:
+                    log.info("iteration %d : teacher loss : %f" % (it, float(out["teacher_loss"])))
             if it > 0 and it % a["val_interval"] == 0:
                 sync_for_validation(ctx, step)   # (data-parallel) replicas equal, else raise; rank 0's BatchNorm statistics into every replica
                 model.eval()
